@@ -19,6 +19,15 @@ overlapped: what a policy that needs obs(t) for a(t + 1) gets), `weak_scaling_12
     python bench.py [--gpus N] [--steps K] [--warmup W]          # N > 1 without a launcher: starts its own N ranks
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
 
+A plain run measures the headline alone: set-up, pre-roll, W warm-up steps, ONE timed region of exactly K steps (`value`,
+`ms_per_step`), the result line.  `--full` adds every side measurement: the headline becomes the median of six timed regions of
+K steps (`repeats`), and `fresh_reset`, `solver_residual_threshold_1e-7`, `host_inclusive`, `steady_synchronised_clocks`, `shards`,
+`roofline`, `valu`, `other_configs`, `cpu_baseline` (N = 1) or `closed_loop`, `sharded_consumers_no_gather`,
+`weak_scaling_128k_per_gpu` (N > 1) are measured and reported; the --no-* options switch single ones of them off.
+`--dump-outputs DIR` writes the [obs|reward|done] rows of the last timed step (all envs, stacked on rank 0) as DIR/obs.npy,
+DIR/reward.npy and DIR/done.npy (float32); every input (reset seeds, episode clocks, actions) is seeded, so two builds run with
+the same arguments can be compared output for output.
+
 Prints ONE JSON line on rank 0.
 """
 import argparse
@@ -99,7 +108,16 @@ def cpu_baseline(target_cpu_seconds=20.0):
     """CPU baseline on this box's host cores, bounded sample.  Real PyBullet (kind "reference") when it is importable --
     BASELINE.md 3.1 -- otherwise the oracle (CPU port of the same step, double precision; kind "port")."""
     import concurrent.futures as cf
+    import multiprocessing
+    # one worker per CPU this job may use: the affinity mask, capped by OMP_NUM_THREADS where the environment sets it (on a shared host
+    # the mask can list many more cores than one job is given).  Workers are spawned, not forked from this process, which holds the GPU.
     cores = len(os.sched_getaffinity(0))
+    if os.environ.get("OMP_NUM_THREADS", "").isdigit():
+        cores = max(1, min(cores, int(os.environ["OMP_NUM_THREADS"])))
+
+    def pool():
+        return cf.ProcessPoolExecutor(max_workers=cores, mp_context=multiprocessing.get_context("spawn"))
+
     try:
         import pybullet  # noqa: F401
         have_pb = True
@@ -108,7 +126,7 @@ def cpu_baseline(target_cpu_seconds=20.0):
     if have_pb:
         w1, t1 = _pybullet_worker((200, 0))
         steps = max(200, int(target_cpu_seconds / (t1 / w1)))
-        with cf.ProcessPoolExecutor(max_workers=cores) as ex:
+        with pool() as ex:
             res = list(ex.map(_pybullet_worker, [(steps, i + 1) for i in range(cores)]))
         return {"value": sum(r[0] for r in res) / max(r[1] for r in res), "unit": "env-steps/s", "cores": cores, "kind": "reference",
                 "single_core": w1 / t1,
@@ -121,7 +139,7 @@ def cpu_baseline(target_cpu_seconds=20.0):
     steps = 16
     n = max(16, total // (cores * steps))
     t0 = time.perf_counter()
-    with cf.ProcessPoolExecutor(max_workers=cores) as ex:
+    with pool() as ex:
         res = list(ex.map(_cpu_worker, [(n, steps, i + 1) for i in range(cores)]))
     wall = time.perf_counter() - t0
     done = sum(r[0] for r in res)
@@ -314,13 +332,37 @@ def parse_args(argv=None):
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--envs", type=int, default=TOTAL_ENVS, help="envs in TOTAL (sharded over the GPUs)")
     ap.add_argument("--preroll", type=int, default=1000, help="untimed steps before the timed region of the headline (steady state)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-fresh", action="store_true", help="skip the extra measurement right after reset()")
-    ap.add_argument("--no-weak", action="store_true", help="skip the extra 131072-envs-per-GPU measurement at N>1")
-    ap.add_argument("--no-host-path", action="store_true", help="skip the host-inclusive pbre_step measurement (N=1 only)")
-    ap.add_argument("--no-other-configs", action="store_true", help="skip the informative iCub / iCub-with-hands lines (N=1 only)")
-    ap.add_argument("--no-shards", action="store_true", help="skip the per-GPU shard sizes of the strong-scaling split measured on this one GPU (N=1 only)")
+    ap.add_argument("--full", action="store_true", help="also every side measurement and check (see the module docstring); off: the headline alone")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write the rows of the last timed step as DIR/{obs,reward,done}.npy (float32)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="(--full) skip the CPU baseline")
+    ap.add_argument("--no-fresh", action="store_true", help="(--full) skip the extra measurement right after reset()")
+    ap.add_argument("--no-weak", action="store_true", help="(--full) skip the extra 131072-envs-per-GPU measurement at N>1")
+    ap.add_argument("--no-host-path", action="store_true", help="(--full) skip the host-inclusive pbre_step measurement (N=1 only)")
+    ap.add_argument("--no-other-configs", action="store_true", help="(--full) skip the informative iCub / iCub-with-hands lines (N=1 only)")
+    ap.add_argument("--no-shards", action="store_true", help="(--full) skip the per-GPU shard sizes of the strong-scaling split measured on this one GPU (N=1 only)")
     return ap.parse_args(argv)
+
+
+DUMP_MAX_BYTES = 64 * 1000 * 1000
+# the keys of a plain run's result line (everything else is --full's)
+PLAIN_KEYS = ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline", "dtype",
+              "data", "full", "config")
+
+
+def dump_outputs(rows, obs_dim, out_dir):
+    """[envs, obs_dim + 2] rows of one step -> out_dir/obs.npy, reward.npy, done.npy (float32).  Should the rows exceed DUMP_MAX_BYTES,
+    a fixed, seeded sample of envs is written instead, with its env indices as env_index.npy."""
+    import numpy as np
+    rows = np.ascontiguousarray(rows, dtype=np.float32)
+    os.makedirs(out_dir, exist_ok=True)
+    if rows.nbytes > DUMP_MAX_BYTES:
+        keep = (DUMP_MAX_BYTES - 4096) // (rows.shape[1] * 4 + 8)      # (the rows, their float64 index, the .npy headers)
+        idx = np.sort(np.random.default_rng(0).choice(rows.shape[0], keep, replace=False))
+        rows = rows[idx]
+        np.save(os.path.join(out_dir, "env_index.npy"), idx.astype(np.float64))
+    np.save(os.path.join(out_dir, "obs.npy"), rows[:, :obs_dim])
+    np.save(os.path.join(out_dir, "reward.npy"), rows[:, obs_dim])
+    np.save(os.path.join(out_dir, "done.npy"), rows[:, obs_dim + 1])
 
 
 def self_launch(args):
@@ -378,7 +420,7 @@ def main():
             dist.init_process_group(backend, rank=rank, world_size=world)
 
     tbl, _ = panda_table()
-    early_other = other_configs(torch, dev) if (os.environ.get("PBRE_BENCH_OTHER_FIRST") == "1" and world == 1) else None     # (diagnostic)
+    early_other = other_configs(torch, dev) if (args.full and os.environ.get("PBRE_BENCH_OTHER_FIRST") == "1" and world == 1) else None     # (diagnostic)
     # a dedicated non-null stream: the kernels and the HIP timing events run on it; RCCL orders itself after it
     side = torch.cuda.Stream(device=dev)
     torch.cuda.set_stream(side)
@@ -557,27 +599,36 @@ def main():
 
     # (side key) right after reset(): no complex env yet (only the step counters differ between envs)
     fresh = None
-    if not args.no_fresh:
+    if args.full and not args.no_fresh:
         fresh = job.timed(args.steps, args.warmup)
         fresh.update({"start_state": "fresh reset() of every env (reference reset_simulation: robots at the home pose, no complex env); step counters de-synchronised", "complex_env_frac_rank0": job.complex_frac()})
 
     # headline: steady state after the pre-roll
     job.preroll(args.preroll - args.warmup)
     csum0 = eng.kernel_info()[7]
-    head = job.timed(args.steps, args.warmup, events=True)
+    # (event pairs around every 8th step with --full only: they feed roofline.step_launch_pair_ms and cost the steps they bracket)
+    head = job.timed(args.steps, args.warmup, events=args.full)
     complex_per_step = ((eng.kernel_info()[7] - csum0) % (1 << 31)) / float(args.steps + args.warmup)
-    # (side key) the same timed region five more times, back to back, without event pairs: the spread of the headline on this box
-    regions = [head] + [job.timed(args.steps, 0) for _ in range(5)]
-    rep = [r["ms_per_step"] for r in regions]
-    region_dev_ms = float(np.median([r["_dev_ms"] for r in regions]))      # device time per launch: median over the same six regions as `ms_per_step`
-    repeats = {"ms_per_step": {"median": float(np.median(rep)), "min": float(np.min(rep)), "max": float(np.max(rep))}, "samples": len(rep),
-               "value_at_median": total * 1e3 / float(np.median(rep)),
-               "note": "six timed regions of exactly --steps steps each on the same stationary batch, back to back (sample 0 with HIP event pairs around every 8th step); `value` is the median's"}
-    # `value` / `ms_per_step`: the MEDIAN of these six timed regions of exactly --steps steps each (the driver's 20 steps are a 4 ms region; a
-    # single one carries the box's scheduling noise); the first region alone is kept as `first_timed_region`
-    first_region = {"ms_per_step": head["ms_per_step"], "value": head["value"]}
-    head["ms_per_step"] = float(np.median(rep)); head["value"] = total * 1e3 / head["ms_per_step"]
+    repeats = first_region = None
+    if args.full:
+        # (side key) the same timed region five more times, back to back, without event pairs: the spread of the headline on this box
+        regions = [head] + [job.timed(args.steps, 0) for _ in range(5)]
+        rep = [r["ms_per_step"] for r in regions]
+        region_dev_ms = float(np.median([r["_dev_ms"] for r in regions]))      # device time per launch: median over the same six regions as `ms_per_step`
+        repeats = {"ms_per_step": {"median": float(np.median(rep)), "min": float(np.min(rep)), "max": float(np.max(rep))}, "samples": len(rep),
+                   "value_at_median": total * 1e3 / float(np.median(rep)),
+                   "note": "six timed regions of exactly --steps steps each on the same stationary batch, back to back (sample 0 with HIP event pairs around every 8th step); `value` is the median's"}
+        # `value` / `ms_per_step` (--full): the MEDIAN of these six timed regions of exactly --steps steps each (20 steps are a 4 ms region; a
+        # single one carries the box's scheduling noise); the first region alone is kept as `first_timed_region`.  A plain run: the one region.
+        first_region = {"ms_per_step": head["ms_per_step"], "value": head["value"]}
+        head["ms_per_step"] = float(np.median(rep)); head["value"] = total * 1e3 / head["ms_per_step"]
+    else:
+        region_dev_ms = head["_dev_ms"]
     steps_before = job.steps_done - args.steps
+    if args.dump_outputs:
+        rows = job.pipe.rows((job.pipe.k - 1) & 1)          # the last timed step's rows, stacked over the ranks on rank 0
+        if rank == 0:
+            dump_outputs(rows.cpu().numpy(), eng.obs_dim, args.dump_outputs)
     complex_after = job.complex_frac()
     finite = bool(torch.isfinite(job.pipe.out[0]).all() and torch.isfinite(job.pipe.out[1]).all())
     comm_kind, comm_note = job.comm_kind, job.comm_note
@@ -595,7 +646,7 @@ def main():
     # (side key, SURVEY section 5 "metrics": contact-count histogram) which contact kinds the envs of the stationary batch are in, from the
     # downloaded state of rank 0's first 16384 envs through the host-side restatement of the step's detection rule (model/contacts.py)
     contact_hist = None
-    if rank == 0:
+    if args.full and rank == 0:
         try:
             from pybullet_robot_envs.model import contacts as _ct
             from pybullet_robot_envs.model.table import panda_table as _pt
@@ -610,7 +661,7 @@ def main():
 
     # (side key, N = 1) Bullet's residual exit on: the stationary batch at the headline size
     rt_side = None
-    if world == 1 and os.environ.get("PBRE_BENCH_NO_RT") != "1":
+    if args.full and world == 1 and os.environ.get("PBRE_BENCH_NO_RT") != "1":
         try:
             rt_side = {str(total): job.timed_with_residual_threshold(max(args.steps, 50))}
         except Exception as e:
@@ -618,7 +669,7 @@ def main():
 
     # extra at N>1: the closed loop (a policy that needs obs(t) to produce a(t + 1): the gather cannot hide behind the next step)
     closed_loop = None
-    if world > 1:
+    if args.full and world > 1:
         if isinstance(job.pipe, CtxGatherPipeline):
             try:
                 closed_loop = job.timed_closed_loop(args.steps, args.warmup)
@@ -630,7 +681,7 @@ def main():
 
     # extra at N>1: the same steps without the gather (every rank's consumer reads its own shard's rows)
     no_gather = None
-    if world > 1:
+    if args.full and world > 1:
         try:
             job.gather = False
             no_gather = clean(job.timed(args.steps, args.warmup))
@@ -640,7 +691,7 @@ def main():
     # extra at N=1: what env.step() delivers through the host-buffer entry point (action upload + kernels + row download
     # through pinned staging buffers, SURVEY 8(d)'s literal metric)
     host = None
-    if world == 1 and not args.no_host_path:
+    if args.full and world == 1 and not args.no_host_path:
         try:
             # (64 i.i.d. action batches on the host: a pool of four, recycled, pushes thousands of envs into joint limits within a few hundred steps)
             g_h = torch.Generator(device=dev); g_h.manual_seed(4242 + rank)
@@ -701,7 +752,7 @@ def main():
     # do not succeed early restart together every 1000 steps): right behind such a mass restart the batch is close to the fresh state,
     # which is what a plain "reset(), 1000 steps, measure" protocol sees
     sync_clocks = None
-    if world == 1 and not args.no_fresh:
+    if args.full and world == 1 and not args.no_fresh:
         try:
             j3 = Job(total, args.steps + args.warmup, desync=False)
             j3.preroll(args.preroll - args.warmup)
@@ -718,7 +769,7 @@ def main():
     # driver's own SCALE runs absent (no 8-GPU node) this is what the 1 -> 8 curve can be projected from: N GPUs step the batch in the
     # time one GPU needs for its 131072 / N shard (+ the gather, which is overlapped).
     shards = None
-    if world == 1 and not args.no_shards and total == TOTAL_ENVS:
+    if args.full and world == 1 and not args.no_shards and total == TOTAL_ENVS:
         shards = {}
         try:
             for n_sh in (65536, 32768, 16384):
@@ -745,7 +796,7 @@ def main():
 
     # extra at N>1: weak scaling -- every GPU keeps the 131072-env shard (131072 x N envs in total), same gather
     weak = None
-    if world > 1 and not args.no_weak:
+    if args.full and world > 1 and not args.no_weak:
         try:
             j2 = Job(total * world, args.steps + args.warmup)
             j2.preroll(args.preroll - args.warmup)
@@ -787,7 +838,7 @@ def main():
             "metric": "env-steps/sec (whole node), Panda-push 128k envs",
             "value": head["value"], "unit": "env-steps/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
             "ms_per_step": head["ms_per_step"], "higher_is_better": True, "scaling": "strong",
-            "vs_baseline": None, "dtype": "f32", "data": "synthetic",
+            "vs_baseline": None, "dtype": "f32", "data": "synthetic", "full": args.full,
             "config": {"workload": "pandaPushGymEnv joint-control step, %d envs in total (%d per GPU), 150 PGS iters, dt 1/240, "
                                    "obj_pose_rnd_std 0.05, tg_pose_rnd_std 0.2, actions U(-1,1) resident in HBM, done envs re-initialised "
                                    "in the step (auto-reset) and counted" % (total, n_local),
@@ -843,9 +894,11 @@ def main():
                                      "source": "profiles/r06_ubench_valu.txt"},
                      "flop_per_env_step": ALG_FLOP_PER_ENV_STEP, "sq_counters": sq, "vgprs_k_fast": info[0], "vgprs_k_fast_rc": info[6], "vgprs_k_step": info[1]},
         }
-        if world == 1 and not args.no_other_configs:
+        if not args.full:      # a plain run: the headline and the configuration it was measured in, nothing else
+            res = dict((k, v) for k, v in res.items() if k in PLAIN_KEYS)
+        if args.full and world == 1 and not args.no_other_configs:
             res["other_configs"] = early_other if early_other is not None else other_configs(torch, dev)
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             try:
                 res["cpu_baseline"] = cpu_baseline()
             except Exception as e:  # the baseline is informative; never lose the GPU line over it

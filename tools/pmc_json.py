@@ -6,13 +6,15 @@ import collections
 import csv
 import glob
 import json
+import os
 import re
 import sys
 
 tag, n_envs = sys.argv[1], int(sys.argv[2])
+OUT = os.environ.get("PBRE_OUT", "out")          # where tools/pmc.sh wrote its passes
 raw = {}
 for cname in ("FETCH_SIZE", "WRITE_SIZE"):
-    f = glob.glob("gpurun_out/pmc_%s_%s/**/*counter_collection.csv" % (tag, cname), recursive=True)[0]
+    f = glob.glob(os.path.join(OUT, "pmc_%s_%s/**/*counter_collection.csv" % (tag, cname)), recursive=True)[0]
     agg = collections.defaultdict(list)
     for r in csv.DictReader(open(f)):
         if r.get("Counter_Name") == cname:
@@ -39,5 +41,5 @@ out = {
          "hbm_bytes_per_env_step": (fetch + write) / n_envs, "algorithmic_bytes_per_env_step": 444,
          "note": "552 B/env of padded record + output accesses, 60 B of solver start values parked in the record, and the register spills around the solver loop"},
 }
-json.dump(out, open("gpurun_out/%s_pmc_hbm.json" % tag, "w"), indent=1)
+json.dump(out, open(os.path.join(OUT, "%s_pmc_hbm.json" % tag), "w"), indent=1)
 print(json.dumps(out[kf], indent=1))

@@ -2,11 +2,12 @@
 # SQ issue counters of the step kernels in one --pmc pass (8 SQ slots); no other tracing domains.
 TAG=$1; shift
 ROOTDIR=$(pwd); export TMPDIR=/tmp
+OUT=${PBRE_OUT:-out}; mkdir -p "$OUT"; OUT=$(cd "$OUT" && pwd)      # results (PBRE_OUT, default out/)
 C="SQ_WAVES SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_INSTS_VALU SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_ANY SQ_WAIT_ANY SQ_WAIT_INST_ANY"
-(cd /tmp && timeout 600 rocprofv3 --pmc $C --output-format csv -d $ROOTDIR/gpurun_out/pmcsq_$TAG -o run -- python $ROOTDIR/bench.py --no-cpu-baseline --no-other-configs --no-host-path --preroll 200 "$@" > $ROOTDIR/gpurun_out/pmcsq_$TAG.log 2>&1)
-f=$(find gpurun_out/pmcsq_$TAG -name "*counter_collection.csv" | head -1)
+(cd /tmp && timeout 600 rocprofv3 --pmc $C --output-format csv -d $OUT/pmcsq_$TAG -o run -- python $ROOTDIR/bench.py --full --no-cpu-baseline --no-other-configs --no-host-path --preroll 200 "$@" > $OUT/pmcsq_$TAG.log 2>&1)
+f=$(find $OUT/pmcsq_$TAG -name "*counter_collection.csv" | head -1)
 echo "== $f"
-[ -n "$f" ] && python - "$f" <<'PY'
+[ -n "$f" ] && python - "$f" "$OUT" <<'PY'
 import csv, sys, collections, json
 rows = list(csv.DictReader(open(sys.argv[1])))
 agg = collections.defaultdict(lambda: collections.defaultdict(list))
@@ -24,6 +25,6 @@ for k, d in out.items():
     if d.get("SQ_WAVES"):
         d["valu_insts_per_wave"] = d.get("SQ_INSTS_VALU", 0) / d["SQ_WAVES"]
 print(json.dumps(out, indent=1))
-json.dump(out, open("gpurun_out/pmcsq_%s.json" % sys.argv[1].split("pmcsq_")[1].split("/")[0], "w"), indent=1)
+json.dump(out, open("%s/pmcsq_%s.json" % (sys.argv[2], sys.argv[1].split("pmcsq_")[1].split("/")[0]), "w"), indent=1)
 PY
-find gpurun_out/pmcsq_$TAG -name "*.csv" -size +6M -delete; find gpurun_out/pmcsq_$TAG -name "*.db" -delete
+find $OUT/pmcsq_$TAG -name "*.csv" -size +6M -delete; find $OUT/pmcsq_$TAG -name "*.db" -delete
