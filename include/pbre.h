@@ -275,8 +275,21 @@ int pbre_get_physics(const pbre_ctx* ctx, pbre_physics* phys);
  * friction stay what pbre_physics says (obj_inertia: principal inertias about the object's axes).  A scene change like any other: the
  * settled snapshot is stale until the next full pbre_reset.  Hull objects are stepped by the general 16-/32-/64-lane row kernels of
  * every engine (the lane-per-env fast paths are compiled for the primitives).  pbre_set_physics with another obj_shape drops the hull;
- * with PBRE_SHAPE_HULL it keeps it.  PBRE_E_ARG: bad count, non-finite or degenerate (flat) vertex set, more faces than PBRE_HULL_MAXF. */
-enum { PBRE_HULL_MAXV = 32, PBRE_HULL_MAXF = 64 };
+ * with PBRE_SHAPE_HULL it keeps it.  PBRE_E_ARG: bad count, non-finite or degenerate (flat) vertex set, more faces than PBRE_HULL_MAXF.
+ *
+ * A COMPOUND of convex pieces (a V-HACD decomposition, what Bullet collides as a btCompoundShape of convex hulls): verts holds up to
+ * PBRE_HULL_MAXP pieces one after the other, separated by one row of three NaNs; each piece is a hull as above (4..PBRE_HULL_MAXV
+ * vertices, <= PBRE_HULL_MAXF triangles), n_verts counts the separator rows too.  A list without a separator is a single hull, exactly
+ * as before.  obj_shape stays PBRE_SHAPE_HULL; obj_h becomes the half extents of the union's bounding box about the origin (the centre
+ * of mass of the whole object).  Against the table / ground the candidates are the vertices of all pieces, piece by piece; only a
+ * piece's PBRE_NC_OT deepest vertices within the margin can take a slot.  The PBRE_NC_OT slots go (1) to the deepest vertex of every
+ * piece that has one within the margin; (2) when exactly two pieces have one, also to each piece's candidate farthest from its deepest
+ * (so that a flat two-piece object rests on two spans instead of three points on one piece and one on the other); (3) the rest to the
+ * deepest of the remaining candidates.  Ties go to the lower index; slots are filled in candidate order; with one piece in touch the
+ * slots are its PBRE_NC_OT deepest, the single hull's rule.  Against a robot sphere the nearest piece
+ * gives the sphere's one contact.  PBRE_E_ARG also for an empty piece, more than PBRE_HULL_MAXP pieces, a row that is partly NaN, or
+ * +-Inf anywhere; on any error the previous object stays in place. */
+enum { PBRE_HULL_MAXV = 32, PBRE_HULL_MAXF = 64, PBRE_HULL_MAXP = 4 };
 int pbre_set_object_hull(pbre_ctx* ctx, const double* verts, int32_t n_verts);
 /* pbre_physics.solver_residual_threshold > 0: the number of sweeps every env's solver ran in the most recent simulation step
  * (1..solver_iters; solver_iters when the test never fired), host [num_envs] int32.  PBRE_E_UNSUPPORTED while the threshold is 0. */

@@ -362,12 +362,15 @@ struct Core {
     // selected) and, when no lane of the wave is nearer, the face loop is skipped.  Otherwise per lane: the nearest face plane if the centre
     // is behind every face (inside: the box / cylinder rule), else the closest point over the face triangles (Ericson, Real-Time Collision
     // Detection 5.1.5, written with selects in the priority order of its early returns: vertex A, B, edge AB, vertex C, edge AC, BC, face).
-    static PBRE_HD F sphere_hull(const float* H, int nf, float rb, const V3& sc, F sr, const V3& bc, const M3& Rb, F margin, V3& n, V3& pb) {
+    // Tf: the first of the nf triangles.  PIECE: one piece of a compound, whose bounding sphere (radius rb) is centred on ctr (object frame)
+    // rather than on the origin.
+    template <bool PIECE = false>
+    static PBRE_HD F sphere_hull(const float* Tf, int nf, float rb, const float* ctr, const V3& sc, F sr, const V3& bc, const M3& Rb, F margin, V3& n, V3& pb) {
         const F one = L::c(1.f), zero = L::c(0.f);
         V3 d = sub(sc, bc);
         V3 p = mtv(Rb, d);
         F len0 = norm(p);
-        F far = len0 - L::c(rb) - sr;
+        F far = (PIECE ? norm(sub(p, v3(L::c(ctr[0]), L::c(ctr[1]), L::c(ctr[2])))) : len0) - L::c(rb) - sr;
         B near = L::lt(far, margin);
         F il0 = one / L::max(len0, L::c(1e-30f));
         n = v3(L::sel(L::gt(len0, zero), d.x * il0, zero), L::sel(L::gt(len0, zero), d.y * il0, zero), L::sel(L::gt(len0, zero), d.z * il0, one));
@@ -376,7 +379,7 @@ struct Core {
         F best2 = L::c(3e38f), maxsd = L::c(-3e38f);
         V3 bcp = v3(zero, zero, zero), nin = v3(zero, zero, one);
         for (int f = 0; f < nf; f++) {
-            const float* T = H + HULL_T0 + 12 * f;
+            const float* T = Tf + 12 * f;
             const V3 a = v3(L::loadu(T + 0), L::loadu(T + 1), L::loadu(T + 2)), ab = v3(L::loadu(T + 3), L::loadu(T + 4), L::loadu(T + 5));
             const V3 ac = v3(L::loadu(T + 6), L::loadu(T + 7), L::loadu(T + 8)), nr = v3(L::loadu(T + 9), L::loadu(T + 10), L::loadu(T + 11));
             const V3 ap = sub(p, a);
@@ -445,6 +448,62 @@ struct Core {
         PBRE_UNROLL for (int i = 0; i < W; i++) {
             F ci = L::bcast(cf, i);
             rank = rank + L::sel(L::lti(L::ci(i), lane), ci, L::c(0.f));
+        }
+        return L::seli(chosen, L::ftoi(rank), L::ci(-1));
+    }
+
+    // The object-table slots of a compound (lanes piece * NC_OT + r hold each piece's candidates x, in candidate order).  Bullet keeps a
+    // manifold of up to 4 points per child of a compound; this is the NC_OT-slot approximation of it:
+    //   1. every piece with a candidate within the margin reserves its deepest one (ties to the lowest lane);
+    //   2. when exactly two pieces are in touch, each also takes, among its candidates (its NC_OT deepest within the margin), the one
+    //      farthest from its reserved one (ties to the lowest lane):
+    //      two spans, whose quadrilateral holds the centre of mass of an object resting on both (with ties to the lower index, plain
+    //      "deepest of the rest" gives one piece 3 slots on one side and the other 1: the object rocks);
+    //   3. the remaining slots go to the deepest of the other candidates within the margin (one piece in touch: its deepest NC_OT).
+    // Returns the per-lane rank in lane order, or -1.
+    static PBRE_HD I select_compound(F dist, B valid, F margin, int np, I lane, const V3& x) {
+        const F zero = L::c(0.f), one = L::c(1.f), big = L::c(3e38f);
+        B cand = L::band(valid, L::lt(dist, margin));
+        if (!L::any(cand)) return L::ci(-1);
+        B chosen = L::bfalse();
+        F d2 = zero, ntouch = zero;
+        for (int p = 0; p < np; p++) {
+            const B inp = L::band(L::bnot(L::lti(lane, L::ci(p * NC_OT))), L::lti(lane, L::ci((p + 1) * NC_OT)));
+            const B res = L::eqi(select_k(dist, L::band(cand, inp), margin, 1, lane), 0);
+            chosen = L::bor(chosen, res);
+            const F at = L::vmin(L::sel(res, L::itof(lane), L::c(999.f)));
+            ntouch = ntouch + L::sel(L::lt(at, L::c(998.f)), one, zero);
+            const V3 xr = bcastvI(x, L::ftoi(L::min(at, L::c((float)(W - 1)))));
+            const V3 e = sub(x, xr);
+            d2 = L::sel(inp, dot(e, e), d2);
+        }
+        const B two = L::eq(ntouch, L::c(2.f));
+        if (L::any(two)) {
+            for (int p = 0; p < np; p++) {
+                const B inp = L::band(L::bnot(L::lti(lane, L::ci(p * NC_OT))), L::lti(lane, L::ci((p + 1) * NC_OT)));
+                const B pool = L::band(L::band(cand, L::bnot(chosen)), L::band(inp, two));
+                const F key = L::sel(pool, zero - d2, big);
+                const F mn = L::vmin(key);
+                const B hit = L::band(L::band(pool, L::eq(key, mn)), L::lt(mn, L::c(1e38f)));
+                const F lk = L::sel(hit, L::itof(lane), L::c(999.f));
+                chosen = L::bor(chosen, L::band(hit, L::eq(lk, L::vmin(lk))));
+            }
+        }
+        for (int r = 0; r < NC_OT; r++) {
+            const B room = L::lt(L::sum(L::sel(chosen, one, zero)), L::c((float)NC_OT - 0.5f));
+            F key = L::sel(L::band(cand, L::bnot(chosen)), dist, big);
+            F mn = L::vmin(key);
+            B hit = L::band(L::band(cand, L::bnot(chosen)), L::eq(key, mn));
+            hit = L::band(hit, L::band(room, L::lt(mn, L::c(1e38f))));
+            F lk = L::sel(hit, L::itof(lane), L::c(999.f));
+            F lm = L::vmin(lk);
+            chosen = L::bor(chosen, L::band(hit, L::eq(lk, lm)));
+        }
+        F cf = L::sel(chosen, one, zero);
+        F rank = zero;
+        PBRE_UNROLL for (int i = 0; i < W; i++) {
+            F ci = L::bcast(cf, i);
+            rank = rank + L::sel(L::lti(L::ci(i), lane), ci, zero);
         }
         return L::seli(chosen, L::ftoi(rank), L::ci(-1));
     }
@@ -785,6 +844,7 @@ struct Core {
                 B infoot = L::band(L::le(L::abs(x.x - L::c(P.tab_c[0])), L::c(P.tab_h[0])), L::le(L::abs(x.y - L::c(P.tab_c[1])), L::c(P.tab_h[1])));
                 return L::sel(L::band(infoot, L::gt(x.z, bot)), top, L::c(P.ground_z));
             };
+            const int hull_np = P.obj_shape == 3 ? (int)P.hull[0] : 0;             // pieces of a hull object (pbre_tables.hpp: HullTable)
             if (P.obj_shape == 3) {
                 // convex hull: every vertex is a candidate.  Lane v holds vertex v + pass * W; with more vertices than lanes each pass keeps its
                 // NC_OT deepest (select_k), their survivors are gathered onto lanes pass * NC_OT + rank -- vertex order is preserved -- and the
@@ -792,25 +852,48 @@ struct Core {
                 // select_contacts over obj_hull[])
                 constexpr int PASSES = (HULL_MAXV + W - 1) / W;
                 static_assert(PASSES * NC_OT <= W, "the survivors of every pass fit one lane group");
-                auto vertex = [&](int pass, B& used) -> V3 {
-                    used = L::lti(lane, L::ci(P.hull_nv - pass * W));
-                    const I at = L::ftoi(L::itof(lane) * L::c(4.f));                 // (lane arithmetic through the float unit: the lane backends have no integer operators)
-                    const float* hv = P.hull + HULL_V0 + 4 * pass * W;
-                    return add(op, mv(Ro, v3(L::loadx(hv, at, used), L::loadx(hv + 1, at, used), L::loadx(hv + 2, at, used))));
+                static_assert(HULL_MAXP * NC_OT <= W, "the survivors of every piece of a compound fit one lane group");
+                auto piece = [&](int v0, int nv, V3& pv, B& pused) {      // the candidates of the nv vertices from vertex v0 on
+                    auto vertex = [&](int pass, B& used) -> V3 {
+                        used = L::lti(lane, L::ci(nv - pass * W));
+                        const I at = L::ftoi(L::itof(lane) * L::c(4.f));                 // (lane arithmetic through the float unit: the lane backends have no integer operators)
+                        const float* hv = P.hull + HULL_V0 + 4 * (v0 + pass * W);
+                        return add(op, mv(Ro, v3(L::loadx(hv, at, used), L::loadx(hv + 1, at, used), L::loadx(hv + 2, at, used))));
+                    };
+                    if (PASSES == 1 || nv <= W) {
+                        pv = vertex(0, pused);
+                    } else {
+                        const F z = L::c(0.f);
+                        pv = v3(z, z, z); pused = L::bfalse();
+                        for (int pass = 0; pass < PASSES; pass++) {
+                            B used_p;
+                            const V3 vp = vertex(pass, used_p);
+                            const F vdp = vp.z - support(vp);
+                            const I rkp = select_k(vdp, used_p, L::c(P.margin), NC_OT, lane);
+                            for (int c = 0; c < NC_OT; c++) {
+                                const Contact cc = fetch(rkp, c, vp, vp, vp, vdp, z, L::ci(0), lane);
+                                const B here = L::band(L::eqi(lane, L::ci(pass * NC_OT + c)), cc.act);
+                                pv = selv(here, cc.pA, pv); pused = L::bor(pused, here);
+                            }
+                        }
+                    }
                 };
-                if (PASSES == 1 || P.hull_nv <= W) {
-                    vx = vertex(0, cand_used);
+                if (hull_np <= 1) {
+                    piece(0, P.hull_nv, vx, cand_used);
                 } else {
+                    // compound: each piece's NC_OT deepest vertices within the margin (what the selection below can take from it: its deepest
+                    // is reserved, the others compete) go to lanes piece * NC_OT + rank, in candidate order
                     const F z = L::c(0.f);
                     vx = v3(z, z, z); cand_used = L::bfalse();
-                    for (int pass = 0; pass < PASSES; pass++) {
-                        B used_p;
-                        const V3 vp = vertex(pass, used_p);
-                        const F vdp = vp.z - support(vp);
-                        const I rkp = select_k(vdp, used_p, L::c(P.margin), NC_OT, lane);
+                    for (int pc = 0; pc < hull_np; pc++) {
+                        const float* D = P.hull + HULL_D0 + HULL_DP * pc;
+                        V3 pv; B pused;
+                        piece((int)D[0], (int)D[2], pv, pused);
+                        const F vdp = pv.z - support(pv);
+                        const I rkp = select_k(vdp, pused, margin, NC_OT, lane);
                         for (int c = 0; c < NC_OT; c++) {
-                            const Contact cc = fetch(rkp, c, vp, vp, vp, vdp, z, L::ci(0), lane);
-                            const B here = L::band(L::eqi(lane, L::ci(pass * NC_OT + c)), cc.act);
+                            const Contact cc = fetch(rkp, c, pv, pv, pv, vdp, z, L::ci(0), lane);
+                            const B here = L::band(L::eqi(lane, L::ci(pc * NC_OT + c)), cc.act);
                             vx = selv(here, cc.pA, vx); cand_used = L::bor(cand_used, here);
                         }
                     }
@@ -823,9 +906,23 @@ struct Core {
             rk_ot = none; rk_ro = none;
             d_ro = L::c(1.f);
             if (obj_on) {
-                rk_ot = select_k(vd, cand_used, margin, NC_OT, lane);
-                d_ro = P.obj_shape == 0 ? sphere_box(sc, sr, op, Ro, oh, n_ro, pB_ro)
-                     : (P.obj_shape == 3 ? sphere_hull(P.hull, P.hull_nf, P.hull_rb, sc, sr, op, Ro, margin, n_ro, pB_ro) : sphere_round(P.obj_shape, sc, sr, op, Ro, oh, n_ro, pB_ro));
+                if (hull_np > 1) {
+                    rk_ot = select_compound(vd, cand_used, margin, hull_np, lane, vx);
+                    // one contact per sphere: the nearest piece's (a piece no lane can reach is skipped inside sphere_hull)
+                    for (int pc = 0; pc < hull_np; pc++) {
+                        const float* D = P.hull + HULL_D0 + HULL_DP * pc;
+                        V3 np_, pbp;
+                        const F dp = sphere_hull<true>(P.hull + HULL_T0 + 12 * (int)D[1], (int)D[3], D[7], D + 4, sc, sr, op, Ro, margin, np_, pbp);
+                        if (pc == 0) { d_ro = dp; n_ro = np_; pB_ro = pbp; continue; }
+                        const B closer = L::lt(dp, d_ro);
+                        d_ro = L::sel(closer, dp, d_ro); n_ro = selv(closer, np_, n_ro); pB_ro = selv(closer, pbp, pB_ro);
+                    }
+                } else {
+                    rk_ot = select_k(vd, cand_used, margin, NC_OT, lane);
+                    d_ro = P.obj_shape == 0 ? sphere_box(sc, sr, op, Ro, oh, n_ro, pB_ro)
+                         : (P.obj_shape == 3 ? sphere_hull(P.hull + HULL_T0, P.hull_nf, P.hull_rb, nullptr, sc, sr, op, Ro, margin, n_ro, pB_ro)
+                                             : sphere_round(P.obj_shape, sc, sr, op, Ro, oh, n_ro, pB_ro));
+                }
                 pA_ro = add(pB_ro, scl(n_ro, d_ro));
                 rk_ro = select_k(d_ro, sv, margin, NC_RO, lane);
             } else { n_ro = up; pB_ro = up; pA_ro = up; }

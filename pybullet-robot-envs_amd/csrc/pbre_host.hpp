@@ -163,10 +163,11 @@ inline bool apply_physics(const pbre_physics& p, Params& P2) {
     return true;
 }
 
-// The face table of a convex-hull object from its vertices (pbre_set_object_hull; layout: pbre_tables.hpp HullTable).  Supporting planes by
-// brute force over the vertex triples (n <= 32), coplanar triples merged into one polygonal face (vertices ordered by angle about the
-// face's centroid, fan-triangulated): at most 2 n - 4 triangles for vertices in general position.  Returns "" or an error text.
-inline std::string build_hull(const double* v, int n, HullTable& H) {
+namespace detail {
+// One convex piece: its vertices go to H.data from vertex H.nv on, its triangles from triangle H.nf on (both counters advance).  Supporting
+// planes by brute force over the vertex triples (n <= 32), coplanar triples merged into one polygonal face (vertices ordered by angle about
+// the face's centroid, fan-triangulated): at most 2 n - 4 triangles for vertices in general position.  Returns "" or an error text.
+inline std::string hull_piece(const double* v, int n, HullTable& H, double lo[3], double hi[3]) {
     if (!v || n < 4 || n > HULL_MAXV) return "pbre_set_object_hull: n_verts must be 4..32";
     double scale = 0;
     for (int i = 0; i < 3 * n; i++) { if (!std::isfinite(v[i])) return "pbre_set_object_hull: non-finite vertex"; scale = std::max(scale, std::fabs(v[i])); }
@@ -196,15 +197,14 @@ inline std::string build_hull(const double* v, int n, HullTable& H) {
         if (!dup) planes.push_back(pl);
     }
     if (planes.size() < 4) return "pbre_set_object_hull: degenerate vertex set (no volume)";
-    H.nv = n; H.nf = 0; H.rb = 0.f;
-    std::memset(H.data, 0, sizeof H.data);
-    double lo[3] = {1e300, 1e300, 1e300}, hi[3] = {-1e300, -1e300, -1e300};
+    const int v0 = H.nv;
     for (int i = 0; i < n; i++) {
         double r2 = 0;
-        for (int k = 0; k < 3; k++) { H.data[HULL_V0 + 4 * i + k] = (float)V(i, k); r2 += V(i, k) * V(i, k); lo[k] = std::min(lo[k], V(i, k)); hi[k] = std::max(hi[k], V(i, k)); }
+        for (int k = 0; k < 3; k++) { H.data[HULL_V0 + 4 * (v0 + i) + k] = (float)V(i, k); r2 += V(i, k) * V(i, k); lo[k] = std::min(lo[k], V(i, k)); hi[k] = std::max(hi[k], V(i, k)); }
         H.rb = std::max(H.rb, (float)std::sqrt(r2));
     }
-    for (int k = 0; k < 3; k++) H.half[k] = std::max(hi[k], -lo[k]);      // (about the origin = the centre of mass: what the rest-height guess of a reset needs)
+    H.nv += n;
+    const int f0 = H.nf;
     for (const Plane& pl : planes) {
         std::vector<int> on;
         double c[3] = {0, 0, 0};
@@ -223,12 +223,56 @@ inline std::string build_hull(const double* v, int n, HullTable& H) {
         }
         std::sort(ang.begin(), ang.end());                            // counter-clockwise about the outward normal
         for (size_t t = 1; t + 1 < ang.size(); t++) {
-            if (H.nf >= HULL_MAXF) return "pbre_set_object_hull: more than 64 triangles";
+            if (H.nf - f0 >= HULL_MAXF) return "pbre_set_object_hull: more than 64 triangles";
             const int a = ang[0].second, b = ang[t].second, cc = ang[t + 1].second;
             float* T = H.data + HULL_T0 + 12 * H.nf++;
             for (int k = 0; k < 3; k++) { T[k] = (float)V(a, k); T[3 + k] = (float)(V(b, k) - V(a, k)); T[6 + k] = (float)(V(cc, k) - V(a, k)); T[9 + k] = (float)pl.n[k]; }
         }
     }
+    return "";
+}
+}   // namespace detail
+
+// The table of a convex-hull object from its vertices (pbre_set_object_hull; layout: pbre_tables.hpp HullTable).  A row of three NaNs
+// separates the pieces of a compound (<= HULL_MAXP pieces of 4..32 vertices each); a list without one is a single hull.  Each piece's
+// directory entry holds its bounding sphere (centre: the middle of its bounding box; a single hull: the origin and hull_rb, as before).
+// Returns "" or an error text; H is only complete on success.
+inline std::string build_hull(const double* v, int n, HullTable& H) {
+    if (!v || n < 4) return "pbre_set_object_hull: n_verts must be 4..32";
+    if (n > HULL_MAXP * (HULL_MAXV + 1) - 1) return "pbre_set_object_hull: n_verts must be 4..131 (up to 4 pieces of 4..32 vertices and the 3 separator rows)";
+    int start[HULL_MAXP + 1], cnt[HULL_MAXP + 1], np = 0, s = 0;
+    for (int i = 0; i <= n; i++) {
+        const bool sep = i < n && std::isnan(v[3 * i]) && std::isnan(v[3 * i + 1]) && std::isnan(v[3 * i + 2]);
+        if (i < n && !sep) continue;
+        if (np == HULL_MAXP) return "pbre_set_object_hull: more than 4 pieces";
+        if (i == s) return "pbre_set_object_hull: empty piece";
+        start[np] = s; cnt[np++] = i - s; s = i + 1;
+    }
+    H.nv = 0; H.nf = 0; H.np = np; H.rb = 0.f;
+    std::memset(H.data, 0, sizeof H.data);
+    H.data[0] = (float)np;
+    double lo[3] = {1e300, 1e300, 1e300}, hi[3] = {-1e300, -1e300, -1e300};
+    for (int p = 0; p < np; p++) {
+        double plo[3] = {1e300, 1e300, 1e300}, phi[3] = {-1e300, -1e300, -1e300};
+        float* D = H.data + HULL_D0 + HULL_DP * p;
+        D[0] = (float)H.nv; D[1] = (float)H.nf;
+        const std::string e = detail::hull_piece(v + 3 * start[p], cnt[p], H, plo, phi);
+        if (!e.empty()) return np > 1 ? e + " (piece " + std::to_string(p) + ")" : e;
+        D[2] = (float)cnt[p]; D[3] = (float)(H.nf - (int)D[1]);
+        double c[3] = {0, 0, 0}, r = H.rb;
+        if (np > 1) {
+            r = 0;
+            for (int k = 0; k < 3; k++) c[k] = 0.5 * (plo[k] + phi[k]);
+            for (int i = 0; i < cnt[p]; i++) {
+                const double* x = v + 3 * (start[p] + i);
+                r = std::max(r, std::sqrt((x[0] - c[0]) * (x[0] - c[0]) + (x[1] - c[1]) * (x[1] - c[1]) + (x[2] - c[2]) * (x[2] - c[2])));
+            }
+            r *= 1.0 + 1e-6;                                                // (a bound: float rounding must not shrink it)
+        }
+        for (int k = 0; k < 3; k++) { D[4 + k] = (float)c[k]; lo[k] = std::min(lo[k], plo[k]); hi[k] = std::max(hi[k], phi[k]); }
+        D[7] = (float)r;
+    }
+    for (int k = 0; k < 3; k++) H.half[k] = std::max(hi[k], -lo[k]);      // (about the origin = the centre of mass: what the rest-height guess of a reset needs)
     return "";
 }
 

@@ -117,7 +117,8 @@ struct Params {                  // float copies of pbre_physics + task constant
                                                     // velocity-level row change |delta impulse / jacDiagABInv| is <= res_lim (Bullet compares the squares); 0: never
     int*  sweeps;                                   // res_lim > 0: per-env count of the sweeps run in the step ([num_envs], this ctx's local env index); may be null
     // PBRE_SHAPE_HULL (obj_shape 3; pbre_set_object_hull): device table [HULL_V0 .. ) = hull_nv vertices x (x, y, z, 0), [HULL_T0 .. ) = hull_nf
-    // triangles x (a[3], ab[3], ac[3], unit outward normal[3]) in the object's frame; hull_rb = the largest vertex distance from the origin
+    // triangles x (a[3], ab[3], ac[3], unit outward normal[3]) in the object's frame; hull_rb = the largest vertex distance from the origin.
+    // A compound (up to HULL_MAXP convex pieces) keeps its piece directory in the table's header [0 .. HULL_V0): hull_nv / hull_nf are the totals
     const float* hull;
     int   hull_nv, hull_nf;
     float hull_rb;
@@ -125,8 +126,13 @@ struct Params {                  // float copies of pbre_physics + task constant
                                                     // once its first word holds this number (its producer is a wave of another block: pbre_capi.hip k_fused)
 };
 
-constexpr int HULL_MAXV = 32, HULL_MAXF = 64, HULL_V0 = 0, HULL_T0 = 4 * HULL_MAXV, HULL_FLOATS = 4 * HULL_MAXV + 12 * HULL_MAXF;
-struct HullTable { int nv = 0, nf = 0; float rb = 0.f; double half[3] = {0, 0, 0}; float data[HULL_FLOATS]; };
+// Hull table (floats): [0] piece count, [HULL_D0 + HULL_DP * p ..] piece p's directory entry -- vertex offset, face offset (in vertices /
+// triangles from HULL_V0 / HULL_T0), vertex count, face count, bounding-sphere centre (x, y, z) and radius, object frame -- then the
+// vertices of all pieces and the triangles of all pieces, piece by piece.  A single hull is a table with one piece (centre 0, radius hull_rb).
+constexpr int HULL_MAXV = 32, HULL_MAXF = 64, HULL_MAXP = 4;          // per piece; pieces per object
+constexpr int HULL_D0 = 4, HULL_DP = 8, HULL_V0 = HULL_D0 + HULL_DP * HULL_MAXP, HULL_T0 = HULL_V0 + 4 * HULL_MAXP * HULL_MAXV;
+constexpr int HULL_FLOATS = HULL_T0 + 12 * HULL_MAXP * HULL_MAXF;
+struct HullTable { int nv = 0, nf = 0, np = 0; float rb = 0.f; double half[3] = {0, 0, 0}; float data[HULL_FLOATS]; };
 
 namespace detail {
 struct Xf { double R[9]; double p[3]; };

@@ -447,8 +447,9 @@ class Engine:
             self.set_object_hull(hull)
 
     def set_object_hull(self, verts):
-        """The object as the convex hull of `verts` ([n, 3], 4 <= n <= 32, object frame, origin = centre of mass): include/pbre.h
-        pbre_set_object_hull.  Mass, inertia and friction stay what set_physics / the constructor's `phys` said."""
+        """The object as the convex hull of `verts` ([n, 3], 4 <= n <= 32, object frame, origin = centre of mass) -- or as a compound of up
+        to 4 such hulls separated by rows of three NaNs (model/objects.py: compound_physics): include/pbre.h pbre_set_object_hull.  Mass,
+        inertia and friction stay what set_physics / the constructor's `phys` said."""
         v = np.ascontiguousarray(verts, dtype=np.float64)
         if v.ndim != 2 or v.shape[1] != 3:
             raise ValueError("verts must be [n, 3]")

@@ -6,6 +6,7 @@ robot's stand-in collision spheres of the RobotTable (model/table.py), the objec
 numpy, vectorised over the batch; float64 (the device tests in float32, so a pair within rounding of the margin may differ)."""
 import numpy as np
 
+from pybullet_robot_envs.model.objects import hull_pieces
 from pybullet_robot_envs.model.table import HEADER, LINK_STRIDE, SPHERE_STRIDE
 
 OBJECT_TABLE, ROBOT_OBJECT, ROBOT_TABLE = 1, 2, 4
@@ -138,7 +139,8 @@ def _shape_candidates(shape, h, Ro):
 def contact_flags(table, state, ndof, phys, no_object=False, hull=None):
     """[N] uint8 of OBJECT_TABLE | ROBOT_OBJECT | ROBOT_TABLE for the batch state records state[N, F] (Q | V | X layout of
     include/pbre.h: joints at [0, ndof), object position / quaternion behind them); phys = pbre_physics (Engine.get_physics()).
-    hull: [nv, 3] vertices of a convex-hull object (phys.obj_shape 3: the vertex set handed to Engine.set_object_hull)."""
+    hull: [nv, 3] vertices of a convex-hull object (phys.obj_shape 3: the vertex set handed to Engine.set_object_hull; a compound's pieces
+    separated by rows of three NaNs, include/pbre.h)."""
     table = np.asarray(table, float)
     st = np.asarray(state, float)
     n = st.shape[0]
@@ -160,7 +162,7 @@ def contact_flags(table, state, ndof, phys, no_object=False, hull=None):
             if shape == 3:
                 if hull is None:
                     raise ValueError("contact_flags: a convex-hull object needs its vertices (hull=)")
-                d_ro = _sphere_hull_dist(sc, rad, op, Ro, np.asarray(hull, float))
+                d_ro = np.min([_sphere_hull_dist(sc, rad, op, Ro, pc) for pc in hull_pieces(hull)], axis=0)      # a compound: the nearest piece
             else:
                 d_ro = _sphere_box_dist(sc, rad, op, Ro, oh) if shape == 0 else _sphere_round_dist(shape, sc, rad, op, Ro, oh)
             flags |= np.where(d_ro < margin, ROBOT_OBJECT, 0).astype(np.uint8)
@@ -168,7 +170,8 @@ def contact_flags(table, state, ndof, phys, no_object=False, hull=None):
     if not no_object:                     # the object's candidate points (box vertices / round primitives) against the table top
         top, bot = tc[2] + th[2], tc[2] - th[2]
         if shape == 3:
-            cand = np.einsum("nij,vj->nvi", Ro, np.asarray(hull, float)); ok = np.ones(cand.shape[:2], bool)      # every vertex is a candidate
+            hv = np.concatenate(hull_pieces(hull))
+            cand = np.einsum("nij,vj->nvi", Ro, hv); ok = np.ones(cand.shape[:2], bool)      # every vertex (of every piece) is a candidate
         else:
             cand, ok = _shape_candidates(shape, oh, Ro)
         for v in range(cand.shape[1]):
