@@ -35,6 +35,8 @@
  *        dof_index(-1 fixed), lateral_friction, effort, velocity, ik_passive (1: a joint the inverse kinematics must not move -- the
  *        virtual joints of a soft-pinned floating base, model/table.py: float_base), reserved[2]
  *   then n_spheres records of 8: link, centre[3], radius, friction, fingertip slot + 1 (0: not a fingertip), reserved
+ *
+ * The batched ray-cast camera (depth, segmentation and colour images of every env) is declared in pbre_camera.h.
  */
 #ifndef PBRE_H
 #define PBRE_H

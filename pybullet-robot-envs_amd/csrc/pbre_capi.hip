@@ -199,14 +199,31 @@ extern "C" {
 int pbre_default_config(pbre_config* cfg, int32_t robot, int32_t task) { return default_config(cfg, robot, task); }
 
 __attribute__((visibility("hidden"))) void pbre_comm_release(const pbre_ctx* c);      // pbre_comm.hip: the ctx's RCCL communicator, if any
+// pbre_camera.hip (include/pbre_camera.h): the camera's per-ctx record -- a copy of the RobotTable (the engines keep lane tables only) -- and its release
+__attribute__((visibility("hidden"))) CamState* pbre_camera_state_new(const double* robot_table, size_t len);
+__attribute__((visibility("hidden"))) void pbre_camera_state_free(CamState* s);
+// ... and what it reads of a ctx of either engine (pbre_wide.hpp: CamView); *cam: the ctx's slot for that record
+__attribute__((visibility("hidden"))) int pbre_camera_view(pbre_ctx* c, CamView* v, void* stream, int host_sync, CamState** cam) {
+    *cam = c->cam;
+    if (c->wide) return wide_cam_view(c->wide, v, stream, host_sync != 0);
+    HIPCHK(hipSetDevice(c->device));
+    if (host_sync) HIPCHK(quiesce(c));
+    else if (stream) c->ext_dirty = true;
+    v->state = c->main.state; v->stride = STATE; v->n = c->n; v->obj_lane = LC; v->device = c->device; v->flags = c->cfg.flags;
+    v->phys = c->cfg.phys; v->hull = c->P.obj_shape == PBRE_SHAPE_HULL ? c->P.hull : nullptr;
+    v->stream = stream == PBRE_STREAM_LEGACY ? nullptr : (stream ? stream : (void*)c->stream);
+    return PBRE_OK;
+}
+__attribute__((visibility("hidden"))) void pbre_camera_set_error(pbre_ctx* c, const char* msg) { if (!c) g_err = msg; else if (c->wide) wide_set_error(c->wide, msg); else c->err = msg; }
 
 void pbre_destroy(pbre_ctx* c) {
     if (!c) return;
     pbre_comm_release(c);
-    if (c->wide) { wide_destroy(c->wide); delete c; return; }
+    if (c->wide) { wide_destroy(c->wide); pbre_camera_state_free(c->cam); delete c; return; }
     (void)hipSetDevice(c->device);
     if (c->stream) (void)hipStreamSynchronize(c->stream);
     if (c->side) (void)hipStreamSynchronize(c->side);
+    pbre_camera_state_free(c->cam); c->cam = nullptr;
     free_buf(c->main); free_buf(c->tmp);
     for (void* p : {(void*)c->dT, (void*)c->d_act, (void*)c->d_out, (void*)c->d_scratch, (void*)c->d_ids, (void*)c->d_ep, (void*)c->d_idx, (void*)c->d_mask, (void*)c->d_bad, (void*)c->d_sweeps, (void*)c->d_hull})
         if (p) (void)hipFree(p);
@@ -234,6 +251,7 @@ int pbre_create(const pbre_config* cfg, pbre_ctx** out) {
     if (table_ndof(*cfg) > NJ || cfg->robot_level) {      // iCub shapes, and the robot-level interface (motor records) of either robot
         const int rc = wide_create(cfg, &c->wide, g_err);
         if (rc != PBRE_OK) { delete c; return rc; }
+        c->cam = pbre_camera_state_new(cfg->robot_table, cfg->robot_table_len);
         *out = c;
         return PBRE_OK;
     }
@@ -311,6 +329,7 @@ int pbre_create(const pbre_config* cfg, pbre_ctx** out) {
         CK(hipStreamSynchronize(c->stream));
     }
 #undef CK
+    c->cam = pbre_camera_state_new(cfg->robot_table, cfg->robot_table_len);
     *out = c;
     return PBRE_OK;
 }

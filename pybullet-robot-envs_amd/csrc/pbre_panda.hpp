@@ -613,6 +613,7 @@ struct pbre_ctx {
     unsigned char* d_mask = nullptr;
     bool ext_dirty = false;            // a pbre_step_device was enqueued on a caller-supplied stream since the last quiesce()
     std::string err;
+    CamState* cam = nullptr;           // the camera's RobotTable copy, visual list and scene buffer (pbre_camera.hip owns it; either engine)
 };
 static inline int ceil16(int n) { return (n + EPB - 1) / EPB * EPB; }
 // (a convex-hull object is stepped by the general row kernel: the lane-per-env kernels are compiled for the primitives)

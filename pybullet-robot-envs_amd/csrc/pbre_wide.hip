@@ -382,6 +382,16 @@ int wide_motor_state(WideEngine* w, float* out, const float* in) {
     if (in) WCHK(hipMemcpy(w->tgt, in, (size_t)w->n * w->tgs * 4, hipMemcpyHostToDevice));
     return PBRE_OK;
 }
+int wide_cam_view(WideEngine* w, CamView* v, void* stream, bool host_sync) {
+    WCHK(hipSetDevice(w->device));
+    if (host_sync) WCHK(wquiesce(w));
+    else if (stream) w->ext_dirty = true;
+    v->state = w->state; v->stride = w->sf; v->n = w->n; v->obj_lane = w->lc; v->device = w->device; v->flags = w->cfg.flags;
+    v->phys = w->cfg.phys; v->hull = w->P.obj_shape == PBRE_SHAPE_HULL ? w->P.hull : nullptr;
+    v->stream = stream == PBRE_STREAM_LEGACY ? nullptr : (stream ? stream : (void*)w->stream);
+    return PBRE_OK;
+}
+void wide_set_error(WideEngine* w, const std::string& msg) { w->err = msg; }
 int wide_get_physics(const WideEngine* w, pbre_physics* p) { *p = w->cfg.phys; return PBRE_OK; }
 int wide_set_physics(WideEngine* w, const pbre_physics* p) {
     Params P2 = w->P;

@@ -34,4 +34,19 @@ int  wide_obs_limits(const WideEngine* w, float* lo, float* hi);
 int  wide_timing(const WideEngine* w, double* ms, int32_t n);
 int  wide_kernel_info(const WideEngine* w, int32_t* info, int32_t n);
 
+// What the camera (pbre_camera.hip, include/pbre_camera.h) reads of an engine -- it writes none of it: the state records [n][stride] floats
+// on the device (object pose at float obj_lane of a record), the scene, the hull table (null without one; its piece directory is in
+// its header, pbre_tables.hpp) and the stream the render goes to.
+struct CamState;      // the camera's own buffers: pbre_ctx::cam
+struct CamView {
+    const float* state; int stride, n, obj_lane, device, flags;
+    pbre_physics phys;
+    const float* hull;
+    void* stream;         // a hipStream_t
+};
+// Fills *v for a render on `stream` (as for pbre_step_device: PBRE_STREAM_LEGACY, a hipStream_t, or null = the engine's own stream).
+// host_sync: a host-synchronous render -- all work of the engine is complete on return (then stream must be null).
+int  wide_cam_view(WideEngine* w, CamView* v, void* stream, bool host_sync);
+void wide_set_error(WideEngine* w, const std::string& msg);
+
 }  // namespace pbre

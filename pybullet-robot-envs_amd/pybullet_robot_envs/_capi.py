@@ -50,6 +50,15 @@ class Config(C.Structure):
                 ("robot_table", C.c_void_p), ("robot_table_len", C.c_size_t)]
 
 
+class Camera(C.Structure):
+    """pbre_camera (include/pbre_camera.h)"""
+    _fields_ = [("view", C.c_float * 16), ("proj", C.c_float * 16), ("per_env_view", C.c_int32), ("views", C.c_void_p),
+                ("width", C.c_int32), ("height", C.c_int32),
+                ("robot_id", C.c_int32), ("table_id", C.c_int32), ("object_id", C.c_int32), ("floor_id", C.c_int32),
+                ("light", C.c_float * 3), ("ambient", C.c_float),
+                ("background", C.c_float * 3), ("floor_rgb", C.c_float * 3), ("table_rgb", C.c_float * 3), ("object_rgb", C.c_float * 3)]
+
+
 _LIB = None
 
 
@@ -86,6 +95,12 @@ def load(path=None):
     lib.pbre_host_alloc.argtypes = [C.c_size_t]
     lib.pbre_host_free.restype = None
     lib.pbre_host_free.argtypes = [C.c_void_p]
+    if hasattr(lib, "pbre_camera_render"):       # the camera (include/pbre_camera.h); the host emulation library has none
+        for name in ("pbre_camera_default", "pbre_camera_set_visuals", "pbre_camera_render_device", "pbre_camera_render"):
+            getattr(lib, name).restype = C.c_int
+        lib.pbre_camera_set_visuals.argtypes = [C.c_void_p, C.c_void_p, C.c_int32]
+        lib.pbre_camera_render_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        lib.pbre_camera_render.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     if path is None:
         _LIB = lib
     return lib
@@ -485,6 +500,84 @@ class Engine:
         self._chk(self.lib.pbre_kernel_info(self._ctx, info, C.c_int32(16)))
         return list(info)
 
+    # ---- the camera (include/pbre_camera.h; csrc/pbre_camera.hip) ----
+    def _need_camera(self):
+        if not hasattr(self.lib, "pbre_camera_render"):
+            raise RuntimeError("render: this library has no camera (no pbre_camera_render symbol; the host emulation library does not render)")
+
+    def make_camera(self, width=64, height=48, view=None, proj=None, views=None, **fields):
+        """A `Camera` with the library's defaults (pbre_camera_default: light, colours, body ids, the task envs' camera about the
+        origin).  view / proj: 16 floats, column major (camera.py); views: [num_envs, 16], one view per env; fields: any other member."""
+        self._need_camera()
+        cam = Camera()
+        rc = self.lib.pbre_camera_default(C.byref(cam), C.c_int32(int(width)), C.c_int32(int(height)))
+        if rc != 0:
+            raise RuntimeError("pbre_camera_default failed (%d): width and height must be at least 1" % rc)
+        if view is not None:
+            cam.view[:] = [float(x) for x in np.asarray(view).reshape(16)]
+        if proj is not None:
+            cam.proj[:] = [float(x) for x in np.asarray(proj).reshape(16)]
+        if views is not None:
+            v = np.ascontiguousarray(views, dtype=np.float32)
+            if v.shape != (self.num_envs, 16):
+                raise ValueError("views must have shape (%d, 16), got %r" % (self.num_envs, v.shape))
+            cam._views_keep = v                  # (the struct only holds the address)
+            cam.views = v.ctypes.data
+            cam.per_env_view = 1
+        for k, val in fields.items():
+            if not hasattr(cam, k):
+                raise TypeError("unknown pbre_camera field %r" % k)
+            if isinstance(val, (list, tuple, np.ndarray)):
+                getattr(cam, k)[:] = [float(x) for x in val]
+            else:
+                setattr(cam, k, val)
+        return cam
+
+    def set_visuals(self, records=None):
+        """The robot's visual primitives, [n, 12] (model/visuals.py); None or empty: the RobotTable's collision spheres alone."""
+        self._need_camera()
+        r = np.zeros((0, 12), np.float32) if records is None else np.ascontiguousarray(records, dtype=np.float32).reshape(-1, 12)
+        self._chk(self.lib.pbre_camera_set_visuals(self._ctx, _fp(r) if len(r) else None, C.c_int32(len(r))))
+        self._visuals_set = True
+
+    def render(self, camera=None, width=64, height=48, depth=True, seg=True, rgb=True, out="numpy"):
+        """Images of every env: a dict with "depth" float32 [N, H, W] (metres along the view axis), "seg" int32 [N, H, W] (PyBullet's
+        body + ((link + 1) << 24), -1 background) and "rgba" uint8 [N, H, W, 4], each only when asked for.  camera: a `Camera`
+        (make_camera) or None = the default camera at width x height.  out="numpy": host arrays, synchronous.  out="torch": tensors on
+        the engine's device, rendered on torch's current stream behind whatever step was enqueued there (asynchronous)."""
+        self._need_camera()
+        if not getattr(self, "_visuals_set", False):
+            from pybullet_robot_envs.model.visuals import default_visuals
+            self.set_visuals(default_visuals(self._table))
+        cam = camera if camera is not None else self.make_camera(width, height)
+        shape = (self.num_envs, int(cam.height), int(cam.width))
+        if shape[1] < 1 or shape[2] < 1 or shape[0] * shape[1] * shape[2] > 2 ** 31 - 1:      # (the library says why; allocate nothing)
+            self._chk(self.lib.pbre_camera_render(self._ctx, C.byref(cam), None, None, None))
+        res = {}
+        if out == "torch":
+            import torch
+            dev = torch.device("cuda", int(self.cfg.device_id))
+            if depth:
+                res["depth"] = torch.empty(shape, dtype=torch.float32, device=dev)
+            if seg:
+                res["seg"] = torch.empty(shape, dtype=torch.int32, device=dev)
+            if rgb:
+                res["rgba"] = torch.empty(shape + (4,), dtype=torch.uint8, device=dev)
+            ptr = lambda k: C.c_void_p(res[k].data_ptr()) if k in res else None
+            self._chk(self.lib.pbre_camera_render_device(self._ctx, C.byref(cam), ptr("depth"), ptr("seg"), ptr("rgba"), C.c_void_p(torch_stream(dev))))
+            return res
+        if out != "numpy":
+            raise ValueError("render: out must be 'numpy' or 'torch'")
+        if depth:
+            res["depth"] = np.empty(shape, np.float32)
+        if seg:
+            res["seg"] = np.empty(shape, np.int32)
+        if rgb:
+            res["rgba"] = np.empty(shape + (4,), np.uint8)
+        ptr = lambda k: _fp(res[k]) if k in res else None
+        self._chk(self.lib.pbre_camera_render(self._ctx, C.byref(cam), ptr("depth"), ptr("seg"), ptr("rgba")))
+        return res
+
 
 class MultiEngine(object):
     """`num_envs` environments sharded over several GPUs of one node from ONE process (the Gym classes' `devices=[...]` kwarg, SURVEY
@@ -526,6 +619,9 @@ class MultiEngine(object):
 
     def obs_limits(self):
         return self.shards[0].obs_limits()
+
+    def render(self, *a, **kw):
+        raise NotImplementedError("render: one device per engine")
 
     def reset(self, mask=None):
         m = None if mask is None else np.ascontiguousarray(mask, dtype=np.uint8)

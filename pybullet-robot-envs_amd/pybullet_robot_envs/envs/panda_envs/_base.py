@@ -29,7 +29,7 @@ class PandaTaskBase(Env):
         self._use_IK = use_IK
         self._action_repeat = action_repeat
         self._observation = []
-        self._renders = renders        # accepted for API parity; there is no GUI (render() returns an empty array)
+        self._renders = renders        # accepted for API parity; there is no GUI (render("rgb_array") returns images)
         self._max_steps = max_steps
         self._target_dist_min = target_dist_min
         self._tg_pose_rnd_std = tg_pose_rnd_std
@@ -187,10 +187,29 @@ class PandaTaskBase(Env):
         self._robot.seed(seed)
         return [seed]
 
-    def render(self, mode="rgb_array"):
-        # no camera in the batched engine (the reference's own render() is broken: it reads an unset self._p,
-        # panda_push_gym_env.py:267)
-        return np.array([])
+    def _camera(self, width, height):
+        """The reference's camera (panda_push_gym_env.py:267-286, icub_reach_gym_env.py: the same): it looks at the robot's base from
+        1.3 m, yaw 180, pitch -40; fov 60, near 0.1, far 100."""
+        from pybullet_robot_envs import camera as cam
+        base = np.asarray(self._robot.robot_table[6:9], float)
+        view = cam.view_matrix_from_yaw_pitch_roll(base, 1.3, 180, -40, 0, 2)
+        proj = cam.projection_matrix_fov(60, float(width) / height, 0.1, 100.0)
+        return self._engine.make_camera(width, height, view=view, proj=proj, robot_id=self._robot.robot_id,
+                                        table_id=self._world.table_id, object_id=self._world.obj_id)
+
+    def render(self, mode="rgb_array", width=480, height=640):
+        """mode "rgb_array": uint8 [N, H, W, 3] ([H, W, 3] for one env) from the batched ray-cast camera (include/pbre_camera.h; the
+        reference's size, RENDER_WIDTH 480 x RENDER_HEIGHT 640, by default).  Any other mode: an empty array, as in the reference."""
+        if mode != "rgb_array":
+            return np.array([])
+        img = self._engine.render(self._camera(width, height), depth=False, seg=False, rgb=True)["rgba"]
+        return self._squeeze(np.ascontiguousarray(img[..., :3]))
+
+    def render_tensor(self, width=84, height=84, depth=True, seg=True, rgb=True):
+        """Image observations without a host hop: the dict of `Engine.render(out="torch")` -- "depth" float32 [N, H, W], "seg" int32
+        [N, H, W], "rgba" uint8 [N, H, W, 4] tensors on the engine's device, rendered on torch's current stream (so after a
+        step_tensor on that stream they show the state it produced)."""
+        return self._engine.render(self._camera(width, height), depth=depth, seg=seg, rgb=rgb, out="torch")
 
     # ------------------------------------------------------------------ reference attributes
     @property
