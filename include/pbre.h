@@ -189,7 +189,7 @@ int pbre_reset_snapshot(pbre_ctx* ctx, const uint8_t* env_mask, float* obs_out);
 int pbre_step(pbre_ctx* ctx, const float* actions, float* out);
 
 /* The same step PIPELINED across calls (round 6; SURVEY 8(d)'s metric counts upload + kernels + download): pbre_step_async enqueues the
- * upload of `actions`, the step and the download of its rows into `out` on three streams and returns; pbre_step_wait blocks until the
+ * upload of `actions` and the step on the ctx's stream and the download of its rows into `out` on a second stream, and returns; pbre_step_wait blocks until the
  * rows of the OLDEST step not yet waited for are in `out`.  At most two steps may be in flight: in an open loop
  *     pbre_step_async(a[0], out[0]);  for t = 1..: { pbre_step_async(a[t], out[t & 1]); pbre_step_wait(); consume out[(t - 1) & 1]; }
  * the download of step t - 1 (the PCIe floor: num_envs x (obs_dim + 2) x 4 bytes) overlaps the kernels of step t and the upload of the

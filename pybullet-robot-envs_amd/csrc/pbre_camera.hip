@@ -15,7 +15,7 @@
 #include <string>
 #include <vector>
 #include "../../include/pbre_camera.h"
-#include "pbre_wide.hpp"
+#include "pbre_engine.hpp"
 #include "pbre_tables.hpp"
 #define PBRE_HD __host__ __device__ __forceinline__
 #include "pbre_camera.hpp"
@@ -295,15 +295,6 @@ static std::vector<float> build_device_table(const CamState& s, int& nprims) {
     return out;
 }
 
-#define CAMCHK(call)                                                                                    \
-    do {                                                                                                \
-        hipError_t e_ = (call);                                                                         \
-        if (e_ != hipSuccess) {                                                                         \
-            pbre_camera_set_error(ctx, (std::string(#call) + ": " + hipGetErrorString(e_)).c_str());    \
-            return PBRE_E_DEVICE;                                                                       \
-        }                                                                                               \
-    } while (0)
-
 static int fail(pbre_ctx* ctx, int code, const char* msg) { pbre_camera_set_error(ctx, msg); return code; }
 
 static int check_camera(pbre_ctx* ctx, const pbre_camera* cam) {
@@ -326,29 +317,29 @@ static int render_on(pbre_ctx* ctx, CamState* s, const CamView& v, const pbre_ca
     if (s->dirty) {
         int np = 0;
         const std::vector<float> tab = build_device_table(*s, np);
-        CAMCHK(hipDeviceSynchronize());          // (rare: a render on another stream may still read the old table)
+        PBRE_CHK_ON(ctx, hipDeviceSynchronize());          // (rare: a render on another stream may still read the old table)
         if (tab.size() > s->cap_table) {
-            if (s->d_table) CAMCHK(hipFree(s->d_table));
+            if (s->d_table) PBRE_CHK_ON(ctx, hipFree(s->d_table));
             s->d_table = nullptr; s->cap_table = 0;
-            CAMCHK(hipMalloc(&s->d_table, tab.size() * sizeof(float)));
+            PBRE_CHK_ON(ctx, hipMalloc(&s->d_table, tab.size() * sizeof(float)));
             s->cap_table = tab.size();
         }
-        CAMCHK(hipMemcpy(s->d_table, tab.data(), tab.size() * sizeof(float), hipMemcpyHostToDevice));
+        PBRE_CHK_ON(ctx, hipMemcpy(s->d_table, tab.data(), tab.size() * sizeof(float), hipMemcpyHostToDevice));
         s->nprims = np; s->dirty = false;
     }
     const int sstride = 8 * s->nprims + 16;
     if (v.n > s->cap_n || s->nprims > s->cap_prims) {
-        CAMCHK(hipDeviceSynchronize());
-        for (float** p : {&s->d_frames, &s->d_scene, &s->d_views}) { if (*p) CAMCHK(hipFree(*p)); *p = nullptr; }
+        PBRE_CHK_ON(ctx, hipDeviceSynchronize());
+        for (float** p : {&s->d_frames, &s->d_scene, &s->d_views}) { if (*p) PBRE_CHK_ON(ctx, hipFree(*p)); *p = nullptr; }
         s->cap_n = 0; s->cap_prims = -1;
-        CAMCHK(hipMalloc(&s->d_frames, (size_t)std::max(s->nl, 1) * 12 * v.n * sizeof(float)));
-        CAMCHK(hipMalloc(&s->d_scene, (size_t)v.n * sstride * sizeof(float)));
-        CAMCHK(hipMalloc(&s->d_views, (size_t)v.n * 16 * sizeof(float)));
+        PBRE_CHK_ON(ctx, hipMalloc(&s->d_frames, (size_t)std::max(s->nl, 1) * 12 * v.n * sizeof(float)));
+        PBRE_CHK_ON(ctx, hipMalloc(&s->d_scene, (size_t)v.n * sstride * sizeof(float)));
+        PBRE_CHK_ON(ctx, hipMalloc(&s->d_views, (size_t)v.n * 16 * sizeof(float)));
         s->cap_n = v.n; s->cap_prims = s->nprims;
     }
     if (cam->per_env_view) {                     // (the caller's array may be gone when this call returns: wait for its upload)
-        CAMCHK(hipMemcpyAsync(s->d_views, cam->views, (size_t)v.n * 16 * sizeof(float), hipMemcpyHostToDevice, st));
-        CAMCHK(hipStreamSynchronize(st));
+        PBRE_CHK_ON(ctx, hipMemcpyAsync(s->d_views, cam->views, (size_t)v.n * 16 * sizeof(float), hipMemcpyHostToDevice, st));
+        PBRE_CHK_ON(ctx, hipStreamSynchronize(st));
     }
     RayParams P;
     std::memset(&P, 0, sizeof P);
@@ -370,10 +361,10 @@ static int render_on(pbre_ctx* ctx, CamState* s, const CamView& v, const pbre_ca
     if (P.obj_shape == PBRE_SHAPE_HULL && !P.hull) return fail(ctx, PBRE_E_ARG, "pbre_camera_render: a hull object without a hull table");
     P.depth = d_depth; P.seg = d_seg; P.rgba = (uchar4*)d_rgba;
     hipLaunchKernelGGL(k_cam_scene, dim3((v.n + SCENE_TPB - 1) / SCENE_TPB), dim3(SCENE_TPB), 0, st, s->d_table, v.state, v.stride, v.n, v.obj_lane, s->d_frames, s->d_scene, sstride);
-    CAMCHK(hipGetLastError());
+    PBRE_CHK_ON(ctx, hipGetLastError());
     if (d_depth || d_seg || d_rgba) {
         hipLaunchKernelGGL(k_cam_rays, dim3((unsigned)v.n * (unsigned)P.strips), dim3(CAM_TPB), 0, st, P);
-        CAMCHK(hipGetLastError());
+        PBRE_CHK_ON(ctx, hipGetLastError());
     }
     return PBRE_OK;
 }
@@ -446,9 +437,9 @@ int pbre_camera_render(pbre_ctx* ctx, const pbre_camera* cam, float* depth, int3
     const size_t px = (size_t)v.n * cam->width * cam->height;
     const size_t need = px * 12;                 // depth | seg | rgba, 4 bytes per pixel each
     if (need > s->cap_img) {
-        if (s->d_img) CAMCHK(hipFree(s->d_img));
+        if (s->d_img) PBRE_CHK_ON(ctx, hipFree(s->d_img));
         s->d_img = nullptr; s->cap_img = 0;
-        CAMCHK(hipMalloc(&s->d_img, need));
+        PBRE_CHK_ON(ctx, hipMalloc(&s->d_img, need));
         s->cap_img = need;
     }
     float* dd = depth ? (float*)s->d_img : nullptr;
@@ -456,10 +447,10 @@ int pbre_camera_render(pbre_ctx* ctx, const pbre_camera* cam, float* depth, int3
     uint8_t* dc = rgba ? (uint8_t*)s->d_img + px * 8 : nullptr;
     if ((rc = render_on(ctx, s, v, cam, dd, ds, dc)) != PBRE_OK) return rc;
     hipStream_t st = (hipStream_t)v.stream;
-    if (depth) CAMCHK(hipMemcpyAsync(depth, dd, px * 4, hipMemcpyDeviceToHost, st));
-    if (seg) CAMCHK(hipMemcpyAsync(seg, ds, px * 4, hipMemcpyDeviceToHost, st));
-    if (rgba) CAMCHK(hipMemcpyAsync(rgba, dc, px * 4, hipMemcpyDeviceToHost, st));
-    CAMCHK(hipStreamSynchronize(st));
+    if (depth) PBRE_CHK_ON(ctx, hipMemcpyAsync(depth, dd, px * 4, hipMemcpyDeviceToHost, st));
+    if (seg) PBRE_CHK_ON(ctx, hipMemcpyAsync(seg, ds, px * 4, hipMemcpyDeviceToHost, st));
+    if (rgba) PBRE_CHK_ON(ctx, hipMemcpyAsync(rgba, dc, px * 4, hipMemcpyDeviceToHost, st));
+    PBRE_CHK_ON(ctx, hipStreamSynchronize(st));
     return PBRE_OK;
 }
 

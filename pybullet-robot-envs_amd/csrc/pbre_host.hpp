@@ -146,6 +146,37 @@ inline const char* stale_snapshot_msg() {
     return "the scene changed (pbre_set_physics: geometry / contact parameters) since the last full pbre_reset: the settled snapshot that "
            "pbre_reset_snapshot and PBRE_F_AUTO_RESET restart from is stale -- call pbre_reset for the whole batch first";
 }
+// A scene change (pbre_set_physics with such a change, pbre_set_object_hull): restarts from the old scene's settled snapshot are refused
+// until the next full reset.  P: the parameter block that is about to become the ctx's.
+inline void invalidate_snapshot(bool& have_snapshot, bool& stale_snapshot, Params& P) {
+    stale_snapshot = stale_snapshot || have_snapshot;
+    have_snapshot = false; P.rst_ok = 0;
+}
+// pbre_set_object_hull: a built table -- whose floats the engine keeps at `data` -- becomes the object of the scene
+inline void apply_hull(const HullTable& H, const float* data, pbre_config& cfg, Params& P, bool& have_snapshot, bool& stale_snapshot) {
+    P.hull = data; P.hull_nv = H.nv; P.hull_nf = H.nf; P.hull_rb = H.rb; P.obj_shape = PBRE_SHAPE_HULL;
+    cfg.phys.obj_shape = PBRE_SHAPE_HULL;
+    for (int k = 0; k < 3; k++) { cfg.phys.obj_h[k] = H.half[k]; P.obj_h[k] = (float)H.half[k]; }
+    P.rst_objz = (float)(cfg.h_table + H.half[2]);
+    invalidate_snapshot(have_snapshot, stale_snapshot, P);
+}
+// The apply_action loop of an env.step() (panda_push_gym_env.py:193-242, icub_reach_gym_env.py:200-246): the reference scales the action in
+// place in every iteration, so iteration r applies action * scale^(r+1).  P0: the ctx's parameters, P: those of iteration r (from r - 1's).
+inline void repeat_scale(Params& P, const Params& P0, int r) {
+    P.act_scale = (r ? P.act_scale : 1.f) * P0.act_scale; P.ik_ps = (r ? P.ik_ps : 1.f) * P0.ik_ps; P.ik_rs = (r ? P.ik_rs : 1.f) * P0.ik_rs;
+}
+// pbre_apply_action under Cartesian control: with max_vel the iCub commands every joint (positionGain 0.2, icub_env.py:338-346), the Panda its
+// 7 arm joints with PyBullet's default positionGain 0.1 [EXT-UNVERIFIED] (panda_env.py:284-290).  Returns the velocity bound (0: none).
+inline float apply_action_cmd(Params& P, double max_vel) {
+    const float vm = max_vel > 0 ? (float)max_vel : 0.f;
+    P.cmd_vmax = vm;
+    if (P.robot == PBRE_ROBOT_PANDA && vm > 0.f) { P.cmd_kp = 0.1f; P.cmd_nj = 7; }
+    return vm;
+}
+// what pbre_create returns for an error text of make_tables
+inline int table_error_code(const std::string& e) {
+    return e.find("robot_table") == 0 ? PBRE_E_TABLE : (e.find("not implemented") != std::string::npos ? PBRE_E_UNSUPPORTED : PBRE_E_ARG);
+}
 inline bool apply_physics(const pbre_physics& p, Params& P2) {
     if (p.solver_iters <= 0 || p.dt <= 0 || p.obj_mass <= 0) return false;
     P2.dt = (float)p.dt; P2.inv_dt = (float)(1.0 / p.dt); P2.gz = (float)p.gravity_z; P2.iters = p.solver_iters;

@@ -539,39 +539,34 @@ __global__ __launch_bounds__(LTPB) void kw_lane_classify(const TablesT<Shape32>*
 // count[ccur] describe the current states, a step writes the other halves; the counters rotate over three ints so that the one the
 // step after next appends to is zeroed by a kernel of the current step.
 struct WideLane : WideImpl<Shape32, DevLanes32> {
-    signed char* cls = nullptr;       // [2][n]
-    int* list = nullptr;              // [2][n]
-    int* count = nullptr;             // [3]
+    DevBuf<signed char> cls;          // [2][n]
+    DevBuf<int> list;                 // [2][n]
+    DevBuf<int> count;                // [3]
     int cur = 0, ccur = 0;
     bool cls_valid = false, topo_ok = false, enabled = true;
-    float* dyn = nullptr;             // side buffer of the quad pipeline
+    DevBuf<float> dyn;                // side buffer of the quad pipeline
     hipStream_t side = nullptr;       // kw_obj, the IK kernel and kw_quad_rc run beside kw_dyn / kw_quad; picked per caller stream (pick_side)
     SidePick sp;                      // candidates + calibration (pbre_sidepick.hpp)
-    hipEvent_t ev_fork = nullptr, ev_join = nullptr, ev_dyn = nullptr;
+    Event ev_fork, ev_join, ev_dyn;
     // Cartesian control, round 5: the IK kernel on a stream of its own (highest priority) and per-env "targets complete" marks (ik_done[env] ==
     // ik_seq), so that kw_quad / kw_quad_rc start right behind kw_dyn and only the quads of envs whose IK is still iterating wait
-    hipStream_t ik_stream = nullptr;
-    unsigned long long* ik_done = nullptr;      // [n][ND] the hand-over boxes: (target | sequence number << 32) per DoF
+    Stream ik_stream;
+    DevBuf<unsigned long long> ik_done;         // [n][ND] the hand-over boxes: (target | sequence number << 32) per DoF
     int ik_seq = 0;
     int ik_overlap = 1;               // PBRE_IK_OVERLAP=0: the kernel-level dependency of rounds 2-4 (A/B)
     int rc_epw = 16;                  // envs per wave of kw_quad_rc (PBRE_QUAD_RC_EPW: A/B, measured neutral)
     size_t dyn_cs = 0;
     int n_simd = 1024;
-    ~WideLane() override {
-        for (void* p : {(void*)cls, (void*)list, (void*)count, (void*)dyn, (void*)ik_done}) if (p) (void)hipFree(p);
-        if (ik_stream) (void)hipStreamDestroy(ik_stream);
-        if (ev_fork) (void)hipEventDestroy(ev_fork);
-        if (ev_join) (void)hipEventDestroy(ev_join);
-        if (ev_dyn) (void)hipEventDestroy(ev_dyn);
-        if (ev_ik) (void)hipEventDestroy(ev_ik);
-        sp.destroy();
-    }
     // (round objects -- pbre_physics.obj_shape -- included: the object's own rows are ObjStep's, the robot-object test is Fast::sphere_obj)
     // (not with Bullet's residual exit, pbre_physics.solver_residual_threshold > 0: the pipeline splits an env's rows over kernels, the
     // test is a maximum over all of them -- such a batch is stepped by the lane-group kernel, Core::step<RT>)
     // (nor with a convex-hull object: the pipeline's narrow phase is compiled for the primitives)
     bool lane_ok() const override { return enabled && topo_ok && cls != nullptr && objv != nullptr && !(P.res_lim > 0.f) && P.obj_shape != PBRE_SHAPE_HULL; }
     void lane_invalidate() override { cls_valid = false; }
+    hipError_t drain_side() override {
+        hipError_t e = side ? hipStreamSynchronize(side) : hipSuccess;
+        return (e == hipSuccess && ik_stream) ? hipStreamSynchronize(ik_stream) : e;
+    }
     hipError_t lane_alloc() override {
         const char* knob = getenv("PBRE_ICUB_LANE");
         // Default: the pipeline from 16384 envs on.  Below that its chain of lone-wave kernels (kw_dyn -> kw_quad -> kw_fin) on a
@@ -582,9 +577,9 @@ struct WideLane : WideImpl<Shape32, DevLanes32> {
         topo_ok = lane_topo_matches<TopoICub, Shape32>(T);
         if (!enabled || !topo_ok) return hipSuccess;
         hipError_t e;
-        if ((e = hipMalloc(&cls, 2 * (size_t)n)) != hipSuccess) return e;
-        if ((e = hipMalloc(&list, 2 * (size_t)n * sizeof(int))) != hipSuccess) return e;
-        if ((e = hipMalloc(&count, 3 * sizeof(int))) != hipSuccess) return e;
+        if ((e = hipMalloc(cls.out(), 2 * (size_t)n)) != hipSuccess) return e;
+        if ((e = hipMalloc(list.out(), 2 * (size_t)n * sizeof(int))) != hipSuccess) return e;
+        if ((e = hipMalloc(count.out(), 3 * sizeof(int))) != hipSuccess) return e;
         if (!(getenv("PBRE_ICUB_SIDE") && getenv("PBRE_ICUB_SIDE")[0] == '0')) {      // PBRE_ICUB_SIDE=0: everything in stream order (A/B)
             // highest priority: the complex envs' few waves need a whole SIMD's registers each -- they have to be placed before
             // kw_quad's waves fill every SIMD, or they would run after it
@@ -594,15 +589,15 @@ struct WideLane : WideImpl<Shape32, DevLanes32> {
             side = sp.side;
             const char* ef = getenv("PBRE_EVENT_FENCE");      // (see pbre_capi.hip: device-only dependencies need no system-scope fence)
             const unsigned efl = hipEventDisableTiming | ((ef && ef[0] == '1') ? 0u : (unsigned)hipEventDisableSystemFence);
-            if ((e = hipEventCreateWithFlags(&ev_fork, efl)) != hipSuccess) return e;
-            if ((e = hipEventCreateWithFlags(&ev_join, efl)) != hipSuccess) return e;
-            if ((e = hipEventCreateWithFlags(&ev_dyn, efl)) != hipSuccess) return e;
-            if ((e = hipEventCreateWithFlags(&ev_ik, efl)) != hipSuccess) return e;
+            if ((e = hipEventCreateWithFlags(ev_fork.out(), efl)) != hipSuccess) return e;
+            if ((e = hipEventCreateWithFlags(ev_join.out(), efl)) != hipSuccess) return e;
+            if ((e = hipEventCreateWithFlags(ev_dyn.out(), efl)) != hipSuccess) return e;
+            if ((e = hipEventCreateWithFlags(ev_ik.out(), efl)) != hipSuccess) return e;
             if (const char* ev = getenv("PBRE_IK_OVERLAP")) ik_overlap = atoi(ev);
             if (const char* ev = getenv("PBRE_QUAD_RC_EPW")) rc_epw = std::min(16, std::max(1, atoi(ev)));
             if (ik_overlap) {
-                if ((e = hipStreamCreateWithPriority(&ik_stream, hipStreamNonBlocking, phi)) != hipSuccess) return e;
-                if ((e = hipMalloc(&ik_done, (size_t)n * LaneD::ND * sizeof(unsigned long long))) != hipSuccess) return e;
+                if ((e = hipStreamCreateWithPriority(ik_stream.out(), hipStreamNonBlocking, phi)) != hipSuccess) return e;
+                if ((e = hipMalloc(ik_done.out(), (size_t)n * LaneD::ND * sizeof(unsigned long long))) != hipSuccess) return e;
                 if ((e = hipMemset(ik_done, 0, (size_t)n * LaneD::ND * sizeof(unsigned long long))) != hipSuccess) return e;
             }
         }
@@ -612,7 +607,7 @@ struct WideLane : WideImpl<Shape32, DevLanes32> {
             // depended on where the allocation landed: the same command ran at 0.35 or at 0.6 ms per step from one process to the next
             const size_t npad = ((size_t)n + 15) / 16 * 16 + 1040;
             dyn_cs = npad;
-            if ((e = hipMalloc(&dyn, (size_t)4 * DEL * dyn_cs * sizeof(float))) != hipSuccess) return e;
+            if ((e = hipMalloc(dyn.out(), (size_t)4 * DEL * dyn_cs * sizeof(float))) != hipSuccess) return e;
             if ((e = hipMemset(dyn, 0, (size_t)4 * DEL * dyn_cs * sizeof(float))) != hipSuccess) return e;
         }
         hipDeviceProp_t pr;
@@ -621,12 +616,12 @@ struct WideLane : WideImpl<Shape32, DevLanes32> {
     }
     long n_lane_steps = 0;
     bool ik_pending = false;          // Cartesian control: the IK kernel of this step is launched by lane_t (beside kw_dyn, which does not need the targets)
-    hipEvent_t ev_ik = nullptr;
+    Event ev_ik;
     void launch_lane_ik(const float* act, hipStream_t s) override {
         if (side) { ik_pending = true; return; }
         hipLaunchKernelGGL(kw_lane_ik, dim3((n + LTPB - 1) / LTPB), dim3(LTPB), 0, s, dT, P, state, act, tgt, n, act_dim, (unsigned long long*)nullptr, 0);
     }
-    void lane_t(int MODE, const float* act, float* out, int flags, hipStream_t s, hipEvent_t* ek) {
+    void lane_t(int MODE, const float* act, float* out, int flags, hipStream_t s, const Event* ek) {
         signed char* c_cur = cls + (size_t)cur * n; signed char* c_nxt = cls + (size_t)(cur ^ 1) * n;
         int* l_cur = list + (size_t)cur * n; int* l_nxt = list + (size_t)(cur ^ 1) * n;
         int* k_cur = count + ccur; int* k_nxt = count + (ccur + 1) % 3; int* k_zero = count + (ccur + 2) % 3;
@@ -714,7 +709,7 @@ struct WideLane : WideImpl<Shape32, DevLanes32> {
             hipLaunchKernelGGL(kw_lane_classify, dim3((n + LTPB - 1) / LTPB), dim3(LTPB), 0, s, dT, P, state, n, flags, cls, list, count);
             cls_valid = true;
         }
-        hipEvent_t* ek = timed ? ev_k[k_steps % KRING] : nullptr;
+        const Event* ek = timed ? ev_k[k_steps % KRING] : nullptr;
         constexpr int OT = LaneD::M_OBS | LaneD::M_TASK;
         switch (kind) {
             case K_SETTLE: lane_t(0, act, out, flags, s, ek); break;

@@ -85,7 +85,7 @@ __device__ int g_wave_diag;
 #include "lanes_device.hpp"
 #include "pbre_core.hpp"
 #include "pbre_fast.hpp"
-#include "pbre_wide.hpp"
+#include "pbre_engine.hpp"
 #include "pbre_sidepick.hpp"
 
 using namespace pbre;
@@ -538,33 +538,28 @@ __global__ __launch_bounds__(PAIR ? RTPB : FTPB, 2) void k_fused(const FusedArgs
 
 // ------------------------------------------------------------------ context
 struct EnvBuf {                       // a batch of state records with its class bookkeeping
-    float* state = nullptr;           // cap + 16 records
-    signed char* cls = nullptr;       // [2][cap] class per env: cls + cur*cap describes the current state, a step writes the other half (the
+    DevBuf<float> state;              // cap + 16 records
+    DevBuf<signed char> cls;          // [2][cap] class per env: cls + cur*cap describes the current state, a step writes the other half (the
                                       // two kernels of a step run concurrently, so k_fast must not see classes the other one just produced)
-    float* tgt = nullptr;             // [cap + 16][NJ] joint targets of the IK mode
-    int* list[2] = {nullptr, nullptr};  // each [NB][cap]
-    int* count = nullptr;             // [3][NB]: counters rotate over three buffers so that the one the step after next
+    DevBuf<float> tgt;                // [cap + 16][NJ] joint targets of the IK mode
+    DevBuf<int> list[2];              // each [NB][cap]
+    DevBuf<int> count;                // [3][NB]: counters rotate over three buffers so that the one the step after next
                                       // appends to can be zeroed by a kernel of the current step (no memset on the hot path)
     int cur = 0, ccur = 0;            // list[cur] / count + ccur*NB: complex envs of the current state, per class
-    float* objv_g = nullptr;          // [cap + 32][W] k_fused's side records: the object waves' twists for the row waves of other blocks
+    DevBuf<float> objv_g;             // [cap + 32][W] k_fused's side records: the object waves' twists for the row waves of other blocks
     int objv_seq = 0;                 // sequence number of the last k_fused launch (the records' "complete" mark)
-    float* pair_g = nullptr;          // [(cap + 63) / 64] records of PBRE_PAIR_G_BYTES: k_fused's tail pairs (a PairX + per-lane sequence words)
-    int* h_total = nullptr;           // pinned host int the device writes the complex-env count of the step it runs into
+    DevBuf<float> pair_g;             // [(cap + 63) / 64] records of PBRE_PAIR_G_BYTES: k_fused's tail pairs (a PairX + per-lane sequence words)
+    HostBuf<int> h_total;             // pinned host int the device writes the complex-env count of the step it runs into
     int cap = 0;
 };
-
-struct pbre_ctx {
-    WideEngine* wide = nullptr;        // robots with more than 9 DoF (iCub): every entry point forwards to the 64-lane engine
-    pbre_config cfg;
-    Tables T; Params P;
-    int n = 0, npad = 0, obs_dim = 0, act_dim = 0, ow = 0, device = 0;
-    Tables* dT = nullptr;
+// The Panda task engine: the implementation of pbre_ctx (pbre_engine.hpp) for a robot the compiled-in 9-DoF shape holds.  Its methods are in
+// pbre_capi.hip, its step launcher is launch_step_t below.
+struct PandaEngine : pbre_ctx {
+    Tables T;
+    int npad = 0;
+    DevBuf<Tables> dT;
     EnvBuf main, tmp;
-    float *d_act = nullptr, *d_out = nullptr, *d_scratch = nullptr;
-    int* d_bad = nullptr;              // NaN / Inf guard: env-steps that met a non-finite state (Params::bad_count)
-    float* d_hull = nullptr;           // PBRE_SHAPE_HULL: the object's vertex / face table (Params::hull; pbre_set_object_hull)
-    int* d_sweeps = nullptr;           // [npad] sweeps every env's solver ran in the last step (Params::sweeps; pbre_physics.solver_residual_threshold > 0)
-    unsigned long long* d_ids = nullptr; unsigned* d_ep = nullptr; int* d_idx = nullptr;
+    DevBuf<float> d_scratch;
     bool fast_ok = false;
     int n_simd = 1024;
     int rc_first_min = 1;              // complex envs (reported by the device) from which their kernel is scheduled ahead of k_fast
@@ -584,50 +579,59 @@ struct pbre_ctx {
                                        // spill-free build in two half-grid launches back to back, one wave per SIMD each: 0.21 ms against 0.177, profiles/r05_fast3_halves_ab.txt.)
     int fused = 1;                     // the step as ONE launch (k_fused: row-list blocks + fast / pair blocks in one grid); 0: the two kernels on two streams (PBRE_FUSED)
     unsigned long long launches_fused = 0;
-    hipStream_t stream = nullptr, side = nullptr;      // side: the candidate of `sp` that overlaps with the caller's stream
     SidePick sp;
-    hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
+    hipStream_t side = nullptr;        // the candidate of `sp` that overlaps with the caller's stream
     // pipelined host path (pbre_step_async / pbre_step_wait, round 6): two (actions, rows) device buffer pairs and the events that order upload
     // -> step -> download of each slot; created on first use.  The upload rides on the ctx's stream ahead of the step, the download on the side
     // stream the overlap probe picked (pbre_sidepick.hpp: HIP multiplexes streams onto a few hardware queues, and streams that share one do
     // not overlap -- three more streams of their own measured 0.42 ms per step in a small process and 0.95 ms in bench.py's)
     struct AsyncPath {
-        float* d_act[2] = {nullptr, nullptr};
-        float* d_rows[2] = {nullptr, nullptr};
-        hipEvent_t ev_step[2] = {nullptr, nullptr}, ev_out[2] = {nullptr, nullptr};
+        DevBuf<float> d_act[2], d_rows[2];
+        Event ev_step[2], ev_out[2];
         long issued = 0, waited = 0;
         bool ready = false;
     } ap;
     int async_blocks = 128;            // PBRE_ASYNC_BLOCKS: 256-thread blocks of the row-download kernel (k_rows_out)
-    hipEvent_t ev_fork = nullptr, ev_join = nullptr, ev_join_sys = nullptr;   // ev_join_sys: with the system-scope fence (see pbre_step)
+    Event ev_fork, ev_join, ev_join_sys;   // ev_join_sys: with the system-scope fence (see pbre_step)
     bool rows_to_host = false;         // the step in flight writes its output rows straight into page-locked host memory
-    static constexpr int KRING = 64;           // HIP event pairs around the dominant kernel of the last KRING sampled steps,
-    static constexpr int KSAMPLE = 8;          // (every KSAMPLE-th launch is sampled) recorded on the stream that kernel runs on
+    static constexpr int KSAMPLE = 8;          // every KSAMPLE-th launch is sampled into ev_k, on the stream the dominant kernel runs on
     int ksample = KSAMPLE;                     // PBRE_KSAMPLE: A/B of the sampling interval
-    hipEvent_t ev_k[KRING][2] = {};
-    long k_steps = 0, launches = 0, launches3 = 0;      // launches3: steps whose k_fast was the 3-waves-per-SIMD variant
-    double ms[3] = {0, 0, 0};
+    long launches = 0, launches3 = 0;          // launches3: steps whose k_fast was the 3-waves-per-SIMD variant
     int zero_copy = 3;                 // PBRE_ZERO_COPY: pbre_step lets the kernels access page-locked host buffers directly (bit 0 actions, bit 1 rows; 0: staged copies)
-    bool have_snapshot = false;        // a full pbre_reset has recorded the settled snapshot (rst_q, rst_objz)
-    bool stale_snapshot = false;       // ... and a later pbre_set_physics changed the scene it was recorded in
-    unsigned char* d_mask = nullptr;
-    bool ext_dirty = false;            // a pbre_step_device was enqueued on a caller-supplied stream since the last quiesce()
-    std::string err;
-    CamState* cam = nullptr;           // the camera's RobotTable copy, visual list and scene buffer (pbre_camera.hip owns it; either engine)
+
+    int init(const pbre_config& c) override;
+    hipError_t alloc_buf(EnvBuf& b, int cap);
+    hipError_t classify(EnvBuf& b, int cnt, int flags, hipStream_t s);      // (re)build class array and current list of the first cnt envs of b
+    hipError_t settle_steps(EnvBuf& b, int cnt, int count, int flags, hipStream_t s);
+    int async_setup();
+    hipError_t state_changed() override { return classify(main, n, cfg.flags & PBRE_F_NO_OBJECT, stream); }
+    hipError_t drain_side() override { return side ? hipStreamSynchronize(side) : hipSuccess; }      // (also the pipelined host path's downloads: pbre_step_wait then finds their events complete)
+    hipError_t step_repeat(bool last, const float* d_actions, float* d_rows, int flags, hipStream_t s) override;
+    void launch_observe_all(hipStream_t s) override;
+    void launch_snapshot_reset(const unsigned char* mask, hipStream_t s) override;
+    const char* physics_objection(const Params& P2) const override { return fast_ok && !fast_scene_ok(P2) ? "the lane-per-env kernels need explicit joint damping" : nullptr; }
+    void limits(float* lo, float* hi) const override { obs_limits(cfg, T, lo, hi); }
+    int kernel_info(int32_t* info, int32_t cnt) const override;
+    int reset(const uint8_t* mask) override;
+    int settle(int32_t count, int32_t flags) override;
+    int step(const float* actions, float* out) override;
+    int step_async(const float* actions, float* out) override;
+    int step_wait() override;
+    int set_physics_per_env(const uint8_t* mask, const float* obj_mass, const float* obj_mu, const float* obj_lin_damping, const float* robot_lin_damping) override;
 };
 static inline int ceil16(int n) { return (n + EPB - 1) / EPB * EPB; }
 // (a convex-hull object is stepped by the general row kernel: the lane-per-env kernels are compiled for the primitives)
-static inline bool lane_per_env(const pbre_ctx* c) { return c->fast_ok && !(c->cfg.flags & PBRE_F_FORCE_GENERAL) && c->P.obj_shape != PBRE_SHAPE_HULL; }
+static inline bool lane_per_env(const PandaEngine* c) { return c->fast_ok && !(c->cfg.flags & PBRE_F_FORCE_GENERAL) && c->P.obj_shape != PBRE_SHAPE_HULL; }
 
 // one batched step of the first n envs of b on stream s
 template <int MODE, bool RT>
-hipError_t launch_step_t(pbre_ctx* c, EnvBuf& b, int n, const float* act, float* out, int flags, hipStream_t s) {
+hipError_t launch_step_t(PandaEngine* c, EnvBuf& b, int n, const float* act, float* out, int flags, hipStream_t s) {
     // (the per-env sweep counts -- pbre_get_sweeps, residual exit -- are indexed by the env's place in the MAIN buffer; settle and
     // partial-reset steps of the compacted tmp buffer must not write theirs over other envs' counts)
     Params Pk = c->P;
     if (&b != &c->main) Pk.sweeps = nullptr;
     if (!lane_per_env(c)) {
-        hipEvent_t* ek = c->ev_k[c->k_steps % pbre_ctx::KRING];
+        const Event* ek = c->ev_k[c->k_steps % pbre_ctx::KRING];
         (void)hipEventRecord(ek[0], s);
         hipLaunchKernelGGL((k_step<MODE, RT>), dim3(ceil16(n) / EPB), dim3(TPB), 0, s, c->dT, Pk, b.state, act, out, c->d_scratch, n, ceil16(n),
                            c->act_dim, c->ow, flags, b.tgt);
@@ -670,7 +674,7 @@ hipError_t launch_step_t(pbre_ctx* c, EnvBuf& b, int n, const float* act, float*
         // the whole step as one launch on the caller's stream (k_fused): no fork / join through the side stream
         if (c->fused && rows) {
             const bool timed = (c->launches++ % c->ksample) == c->ksample - 1;
-            hipEvent_t* ek = c->ev_k[c->k_steps % pbre_ctx::KRING];
+            const Event* ek = c->ev_k[c->k_steps % pbre_ctx::KRING];
             if (timed) (void)hipEventRecord(ek[0], s);
             c->launches_fused++;
             FusedArgs fa = {c->dT, Pk, b.state, act, out, n, c->act_dim, c->ow, flags, b.cls + (size_t)cur * b.cap, b.cls + (size_t)nxt * b.cap, b.list[cur],
@@ -738,7 +742,7 @@ hipError_t launch_step_t(pbre_ctx* c, EnvBuf& b, int n, const float* act, float*
     // (the last launch of every group of KSAMPLE: the first launches after a reset -- cold instruction cache, first touch of the
     // state -- are warm-up, not samples)
     const bool timed = (c->launches++ % c->ksample) == c->ksample - 1;
-    hipEvent_t* ek = c->ev_k[c->k_steps % pbre_ctx::KRING];
+    const Event* ek = c->ev_k[c->k_steps % pbre_ctx::KRING];
     if (timed) (void)hipEventRecord(ek[0], s_fast);
     // the 3-waves-per-SIMD variant when the complex envs' waves would push k_fast waves of the 2-wave variant into an extra round
     bool fast3 = false;
@@ -776,7 +780,7 @@ hipError_t launch_step_t(pbre_ctx* c, EnvBuf& b, int n, const float* act, float*
 
 
 constexpr int PBRE_STEP_MODES[6] = {0, MODE_SETTLE_IK, MODE_STEP, MODE_STEP_IK, MODE_INNER, MODE_INNER_IK};      // what launch_step<MODE> is called with
-#define PBRE_STEP_INST(KW, M, RT) KW template hipError_t launch_step_t<PBRE_STEP_MODES[M], RT>(pbre_ctx*, EnvBuf&, int, const float*, float*, int, hipStream_t);
+#define PBRE_STEP_INST(KW, M, RT) KW template hipError_t launch_step_t<PBRE_STEP_MODES[M], RT>(PandaEngine*, EnvBuf&, int, const float*, float*, int, hipStream_t);
 #define PBRE_STEP_INST_ALL(KW) PBRE_STEP_INST(KW, 0, false) PBRE_STEP_INST(KW, 1, false) PBRE_STEP_INST(KW, 2, false) PBRE_STEP_INST(KW, 3, false) \
     PBRE_STEP_INST(KW, 4, false) PBRE_STEP_INST(KW, 5, false) PBRE_STEP_INST(KW, 0, true) PBRE_STEP_INST(KW, 1, true) PBRE_STEP_INST(KW, 2, true) \
     PBRE_STEP_INST(KW, 3, true) PBRE_STEP_INST(KW, 4, true) PBRE_STEP_INST(KW, 5, true)

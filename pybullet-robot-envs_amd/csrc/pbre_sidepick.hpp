@@ -9,6 +9,7 @@
 #include <hip/hip_runtime.h>
 #include <cstdio>
 #include <cstdlib>
+#include "pbre_devmem.hpp"
 
 namespace pbre {
 
@@ -19,28 +20,24 @@ static __global__ void k_spin_ticks(long long ticks) {       // busy-wait for `t
 
 struct SidePick {
     static constexpr int NCAND = 4;
-    hipStream_t cand[NCAND] = {nullptr, nullptr, nullptr, nullptr};
+    Stream cand[NCAND];
     hipStream_t side = nullptr;
     struct { hipStream_t s, side; } cache[4] = {};      // picks made so far (caller stream -> side stream), round robin
     int ncache = 0;
-    hipEvent_t t0 = nullptr, t1 = nullptr, fork = nullptr, join = nullptr;
+    Event t0, t1, fork, join;
     int probes = 0;                    // calibration runs so far (diagnostics)
+    ~SidePick() { for (auto& c : cand) if (c) (void)hipStreamSynchronize(c); }      // every candidate idle before it -- and what its kernels use -- is released
     hipError_t create(int priority, bool with_priority) {
         hipError_t e;
         for (auto& c : cand) {
-            e = with_priority ? hipStreamCreateWithPriority(&c, hipStreamNonBlocking, priority) : hipStreamCreateWithFlags(&c, hipStreamNonBlocking);
+            e = with_priority ? hipStreamCreateWithPriority(c.out(), hipStreamNonBlocking, priority) : hipStreamCreateWithFlags(c.out(), hipStreamNonBlocking);
             if (e != hipSuccess) return e;
         }
         side = cand[0];
-        if ((e = hipEventCreate(&t0)) != hipSuccess) return e;
-        if ((e = hipEventCreate(&t1)) != hipSuccess) return e;
-        if ((e = hipEventCreateWithFlags(&fork, hipEventDisableTiming)) != hipSuccess) return e;
-        return hipEventCreateWithFlags(&join, hipEventDisableTiming);
-    }
-    void destroy() {
-        for (auto& c : cand) if (c) { (void)hipStreamSynchronize(c); (void)hipStreamDestroy(c); c = nullptr; }
-        for (hipEvent_t* e : {&t0, &t1, &fork, &join}) if (*e) { (void)hipEventDestroy(*e); *e = nullptr; }
-        side = nullptr;
+        if ((e = hipEventCreate(t0.out())) != hipSuccess) return e;
+        if ((e = hipEventCreate(t1.out())) != hipSuccess) return e;
+        if ((e = hipEventCreateWithFlags(fork.out(), hipEventDisableTiming)) != hipSuccess) return e;
+        return hipEventCreateWithFlags(join.out(), hipEventDisableTiming);
     }
     // the side stream to use beside caller stream s (synchronises s the first time it sees it; PBRE_SIDE_PROBE=0: no calibration)
     hipStream_t pick(hipStream_t s) {

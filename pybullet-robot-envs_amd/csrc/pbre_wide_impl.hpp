@@ -13,7 +13,7 @@
 #include "lanes_device.hpp"
 #include "pbre_core.hpp"
 #include "pbre_objstep.hpp"
-#include "pbre_wide.hpp"
+#include "pbre_engine.hpp"
 
 namespace pbre {
 
@@ -132,47 +132,29 @@ __global__ void kw_target(const Params P, float* __restrict__ state, const unsig
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i < cnt) Core<L, S>::sample_target(P, ids[i], ep[i], state + (size_t)i * S::STATE);
 }
-// shape-independent part of an engine + the launches that depend on the lane-group shape
-struct WideEngine {
-    pbre_config cfg;
-    Params P;
-    int n = 0, obs_dim = 0, act_dim = 0, ow = 0, device = 0, sf = 0, nj = 0, lc = 0, tgs = 0;   // tgs: floats per env of the motor-target buffer
+// The lane-group engines: what pbre_ctx (pbre_engine.hpp) leaves to an engine, written once for every lane-group shape (pbre_wide.hip), and
+// the launches that depend on the shape (WideImpl below)
+struct WideEngine : pbre_ctx {
+    int nj = 0, tgs = 0;                      // tgs: floats per env of the motor-target buffer
     bool mrec = false;                        // the shape keeps persistent motor records (iCub with hands)
-    unsigned char* d_mask = nullptr;
-    float *state = nullptr, *tmp = nullptr, *tgt = nullptr, *tgt_tmp = nullptr;
-    float *d_act = nullptr, *d_out = nullptr;
-    int* d_bad = nullptr;                     // NaN / Inf guard counter (Params::bad_count)
-    float* d_hull = nullptr;                  // PBRE_SHAPE_HULL: the object's vertex / face table (Params::hull; pbre_set_object_hull)
-    int* d_sweeps = nullptr;                  // [n] sweeps every env's solver ran in the last step (Params::sweeps; pbre_physics.solver_residual_threshold > 0)
-    float* objv = nullptr;                    // [n][W] side records of kw_obj, or nullptr: object rows always solved in kw_step
+    DevBuf<float> state_buf, tmp, tgt, tgt_tmp;
+    DevBuf<float> objv;                       // [n][W] side records of kw_obj, or null: object rows always solved in kw_step
     const float* obj_done = nullptr;          // state buffer whose object solve rode along with the last kw_ik launch (consumed by the next step)
-    unsigned long long* d_ids = nullptr; unsigned* d_ep = nullptr; int* d_idx = nullptr;
-    hipStream_t stream = nullptr;
-    hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
-    static constexpr int KRING = 64;
-    hipEvent_t ev_k[KRING][2] = {};
-    long k_steps = 0;
-    double ms[3] = {0, 0, 0};
-    bool ext_dirty = false;                   // a step was enqueued on a caller-supplied stream since the last wquiesce()
-    std::string err;
     enum { K_SETTLE, K_SETTLE_TGT, K_STEP_ACT, K_STEP_TGT, K_INNER_ACT, K_INNER_TGT };
-    virtual ~WideEngine() {}
     virtual std::string tables(const pbre_config& c) = 0;
     virtual hipError_t upload_tables() = 0;
-    virtual void free_tables() = 0;
     virtual void launch_step(int kind, float* st, float* tg, int cnt, const float* act, float* out, int flags, hipStream_t s) = 0;
     virtual void launch_ik(bool reset, float* st, const float* act, float* tg, int cnt, hipStream_t s, bool step_follows = false) = 0;   // step_follows: the next launch on s is launch_step on st
     virtual void launch_observe(bool initd, float* st, float* out, int cnt, hipStream_t s) = 0;
     virtual void launch_init(float* st, int cnt, hipStream_t s) = 0;
-    virtual void launch_snapshot_reset(const unsigned char* mask, hipStream_t s) = 0;
-    bool have_snapshot = false, stale_snapshot = false;   // stale: pbre_set_physics changed the scene the snapshot was recorded in
+    virtual void snapshot_reset_kernels(const unsigned char* mask, hipStream_t s) = 0;      // (the base's launch_snapshot_reset, declared HERE: the order of
+                                                                                            // an engine's virtual functions is the order its kernels are emitted in)
     virtual void launch_target(float* st, int cnt, hipStream_t s) = 0;
     virtual void launch_mrec_init(float* tg, int cnt, hipStream_t s) = 0;
     virtual void launch_set_motors(const MotorCmd& cmd, const unsigned char* mask, hipStream_t s) = 0;
     virtual void launch_cmd_joints(const float* act, float vmax, hipStream_t s) = 0;
     virtual int ndof() const = 0;
     virtual void snapshot(const float* rec) = 0;
-    virtual void limits(float* lo, float* hi) const = 0;
     virtual int vgprs() const = 0;
     // lane-per-env path (pbre_lane.hpp; the Shape32 engine of pbre_wide.hip overrides these): steps of the whole batch on `state`
     virtual bool lane_ok() const { return false; }
@@ -181,6 +163,21 @@ struct WideEngine {
     virtual void launch_lane_ik(const float* act, hipStream_t s) {}
     virtual hipError_t launch_lane_step(int kind, const float* act, float* out, int flags, hipStream_t s, bool timed) { return hipSuccess; }
     virtual int lane_info(int* vg, int* complex_now) { return 0; }
+
+    int init(const pbre_config& c) override;
+    hipError_t wstep(int kind, float* st, float* tg, int cnt, const float* act, float* out, int flags, hipStream_t s, bool timed = false);
+    hipError_t wsettle(float* st, float* tg, int cnt, int count, int flags, hipStream_t s);
+    hipError_t state_changed() override { lane_invalidate(); return hipSuccess; }
+    hipError_t step_repeat(bool last, const float* d_actions, float* d_rows, int flags, hipStream_t s) override;
+    void launch_observe_all(hipStream_t s) override { launch_observe(false, state, d_out, n, s); }
+    void launch_snapshot_reset(const unsigned char* mask, hipStream_t s) override { snapshot_reset_kernels(mask, s); }
+    int kernel_info(int32_t* info, int32_t cnt) const override;
+    int reset(const uint8_t* mask) override;
+    int settle(int32_t count, int32_t flags) override;
+    int reset_snapshot(const uint8_t* mask) override;
+    int set_motors(int32_t cnt, const int32_t* dofs, const float* targets, double kp, double max_force, double max_vel, const uint8_t* mask) override;
+    int apply_action(const float* actions, double max_vel) override;
+    int motor_state(float* out, const float* in) override;
 };
 
 template <class S, class L>
@@ -188,7 +185,7 @@ struct WideImpl : WideEngine {
     using C = Core<L, S>;
     static constexpr int EPB = WTPB / phys_lanes<S>();
     TablesT<S> T;
-    TablesT<S>* dT = nullptr;
+    DevBuf<TablesT<S>> dT;
     static int blocks_of(int cnt) { return (cnt + EPB - 1) / EPB; }
     std::string tables(const pbre_config& c) override {
         std::string e = make_tables<S>(c, T, P);
@@ -196,10 +193,9 @@ struct WideImpl : WideEngine {
         return e;
     }
     hipError_t upload_tables() override {
-        if (!dT) { hipError_t e = hipMalloc(&dT, sizeof(TablesT<S>)); if (e != hipSuccess) return e; }
+        if (!dT) { hipError_t e = hipMalloc(dT.out(), sizeof(TablesT<S>)); if (e != hipSuccess) return e; }
         return hipMemcpy(dT, &T, sizeof(TablesT<S>), hipMemcpyHostToDevice);
     }
-    void free_tables() override { if (dT) (void)hipFree(dT); dT = nullptr; }
     template <int MODE>
     void step_t(float* st, float* tg, int cnt, const float* act, float* out, int flags, hipStream_t s) {
         if (P.res_lim > 0.f) {         // Bullet's residual exit: one solve over all rows of an env, no side solve of the object
@@ -240,7 +236,7 @@ struct WideImpl : WideEngine {
         if (initd) hipLaunchKernelGGL((kw_observe<S, L, C::M_INITD>), dim3(blocks_of(cnt)), dim3(WTPB), 0, s, dT, P, st, out, cnt, ow);
         else hipLaunchKernelGGL((kw_observe<S, L, C::M_OBS>), dim3(blocks_of(cnt)), dim3(WTPB), 0, s, dT, P, st, out, cnt, ow);
     }
-    void launch_snapshot_reset(const unsigned char* mask, hipStream_t s) override {
+    void snapshot_reset_kernels(const unsigned char* mask, hipStream_t s) override {
         hipLaunchKernelGGL((kw_snapshot_reset<S, L>), dim3((n + 127) / 128), dim3(128), 0, s, dT, P, state, mask, n);
         if (P.robot >= 1 && P.task >= 1) {          // icub_push_gym_env.py:124-127: distances of the new episode's first state
             (void)hipMemcpyAsync(tmp, state, (size_t)n * S::STATE * sizeof(float), hipMemcpyDeviceToDevice, s);

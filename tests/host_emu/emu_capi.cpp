@@ -245,9 +245,7 @@ struct Emu : pbre_ctx {
         const int reps = cfg.action_repeat > 1 ? cfg.action_repeat : 1;
         const Params P0 = P;
         for (int r = 0; r < reps; r++) {
-            // apply_action loop (panda_push_gym_env.py:193-242): the reference scales the action in place in every iteration, so
-            // iteration r applies action * scale^(r+1); all but the last iteration only simulate, test termination and count
-            P.act_scale = (r ? P.act_scale : 1.f) * P0.act_scale; P.ik_ps = (r ? P.ik_ps : 1.f) * P0.ik_ps; P.ik_rs = (r ? P.ik_rs : 1.f) * P0.ik_rs;
+            repeat_scale(P, P0, r);        // all but the last iteration only simulate, test termination and count
             const bool last = r + 1 == reps;
             const int tail = last ? (CoreH::M_OBS | CoreH::M_TASK) : (CoreH::M_TASK | CoreH::M_INNER);
             for (int e = 0; e < n; e++) {
@@ -277,10 +275,8 @@ struct Emu : pbre_ctx {
     int apply_action(const float* actions, double max_vel) override {
         if (!S::MREC) { err = "pbre_apply_action: only the robot-level engines keep a motor record"; return PBRE_E_UNSUPPORTED; }
         const bool panda = P.robot == PBRE_ROBOT_PANDA;
-        const float vm = max_vel > 0 ? (float)max_vel : 0.f;
         const Params P0 = P;
-        P.cmd_vmax = vm;
-        if (panda && vm > 0.f) { P.cmd_kp = 0.1f; P.cmd_nj = 7; }       // same host logic as wide_apply_action (pbre_wide.hip)
+        const float vm = apply_action_cmd(P, max_vel);
         for (int e = 0; e < n; e++) {
             float* m = &tgt[(size_t)e * TG];
             const float* a = actions + (size_t)e * act_dim;
@@ -313,7 +309,7 @@ static int create(const pbre_config* cfg, pbre_ctx** out) {
     Emu<S>* c = new Emu<S>();
     c->cfg = *cfg;
     std::string e = make_tables<S>(*cfg, c->T, c->P);
-    if (!e.empty()) { g_err = e; delete c; return e.find("robot_table") == 0 ? PBRE_E_TABLE : (e.find("not implemented") != std::string::npos ? PBRE_E_UNSUPPORTED : PBRE_E_ARG); }
+    if (!e.empty()) { g_err = e; delete c; return table_error_code(e); }
     c->cfg.robot_table = nullptr;
     c->P.bad_count = &c->n_bad;
     c->n = cfg->num_envs; c->obs_dim = obs_dim_of(c->T, c->P); c->act_dim = act_dim_of(*cfg); c->sf = S::STATE; c->nj = S::NJ;
@@ -469,7 +465,7 @@ int pbre_set_physics(pbre_ctx* c, const pbre_physics* phys) {
     Params P2 = c->P;
     if (!apply_physics(*phys, P2)) { c->err = "bad physics parameters"; return PBRE_E_ARG; }
     if (c->fast_ok && !fast_scene_ok(P2)) { c->err = "the lane-per-env kernels need explicit joint damping"; return PBRE_E_UNSUPPORTED; }
-    if (snapshot_relevant_change(c->cfg.phys, *phys)) { c->stale_snapshot = c->stale_snapshot || c->have_snapshot; c->have_snapshot = false; P2.rst_ok = 0; }
+    if (snapshot_relevant_change(c->cfg.phys, *phys)) invalidate_snapshot(c->have_snapshot, c->stale_snapshot, P2);
     c->cfg = cfg; c->P = P2;
     return PBRE_OK;
 }
@@ -479,11 +475,7 @@ int pbre_set_object_hull(pbre_ctx* c, const double* verts, int32_t n_verts) {   
     std::unique_ptr<HullTable> H(new HullTable);
     const std::string e = build_hull(verts, n_verts, *H);
     if (!e.empty()) { c->err = e; return PBRE_E_ARG; }
-    c->P.hull = H->data; c->P.hull_nv = H->nv; c->P.hull_nf = H->nf; c->P.hull_rb = H->rb; c->P.obj_shape = PBRE_SHAPE_HULL;
-    c->cfg.phys.obj_shape = PBRE_SHAPE_HULL;
-    for (int k = 0; k < 3; k++) { c->cfg.phys.obj_h[k] = H->half[k]; c->P.obj_h[k] = (float)H->half[k]; }
-    c->P.rst_objz = (float)(c->cfg.h_table + H->half[2]);
-    c->stale_snapshot = c->stale_snapshot || c->have_snapshot; c->have_snapshot = false; c->P.rst_ok = 0;
+    apply_hull(*H, H->data, c->cfg, c->P, c->have_snapshot, c->stale_snapshot);
     keep.push_back(std::move(H));
     return PBRE_OK;
 }

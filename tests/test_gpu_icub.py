@@ -349,3 +349,27 @@ def test_icub_hull_object_from_a_mesh_file(hip_lib, tmp_path, monkeypatch):
     assert np.abs(np.asarray(ph["obj_hull"]).mean(0)).max() < 1e-9           # about the centre of mass (a symmetric solid: its centroid)
     rep = parity.check_icub_contact_states(_capi.Engine, hip_lib, n_each=12, obj_name="duck_vhacd")
     assert rep["states"] == 4 * 12 and rep["complex_envs_stepped"] >= 0
+
+
+def test_icub_auto_reset_refuses_steps_after_a_scene_change(hip_lib):
+    """The stale-snapshot rule on a lane-group engine: with PBRE_F_AUTO_RESET, a change of the scene geometry makes pbre_step and
+    pbre_step_device refuse (the in-kernel restart would use the old scene's settled snapshot) until a full reset re-records it; a change
+    of mass / friction keeps the snapshot."""
+    n = 4
+    eng, ora, info = parity.make_icub_pair(_capi.Engine, hip_lib, n, task=1, control_arm="l", use_ik=1, control_orientation=0, flags=_capi.F_AUTO_RESET)
+    eng.reset()
+    a = np.zeros((n, eng.act_dim), np.float32)
+    eng.step(a)
+    eng.set_physics(obj_mass=0.2, obj_mu=0.7)                    # domain randomisation: the rest pose does not change
+    eng.step(a)
+    eng.set_physics(obj_h=[0.03, 0.03, 0.06])                    # a taller box: other rest height
+    before = eng.get_state()
+    with pytest.raises(RuntimeError, match="stale"):
+        eng.step(a)
+    with pytest.raises(RuntimeError, match="stale"):
+        eng.reset_snapshot(np.ones(n, np.uint8))
+    assert np.array_equal(eng.get_state(), before)               # a refused step steps nothing
+    eng.reset()
+    ob, rw, dn = eng.step(a)
+    assert np.isfinite(ob).all()
+    eng.close()
