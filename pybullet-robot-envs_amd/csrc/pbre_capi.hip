@@ -25,7 +25,7 @@ PBRE_STEP_INST_ALL(extern)      // pbre_step_inst.hip, one translation unit per 
 
 // use_IK = 1: hand-pose update + inverse kinematics -> joint targets (one thread per env).  RESET: targets of the home hand pose.
 template <bool RESET>
-__global__ __launch_bounds__(FTPB) void k_ik(const Tables* __restrict__ T, const Params P, float* __restrict__ state,
+__global__ __launch_bounds__(FTPB) void k_ik(const FTables* __restrict__ T, const Params P, float* __restrict__ state,
                                              const float* __restrict__ actions, float* __restrict__ tgt, int n, int act_dim) {
     const int env = blockIdx.x * FTPB + threadIdx.x;
     if (env >= n) return;
@@ -33,7 +33,7 @@ __global__ __launch_bounds__(FTPB) void k_ik(const Tables* __restrict__ T, const
 }
 
 // Class of every env's current state (after reset / set_state / a change of the NO_OBJECT flag).
-__global__ __launch_bounds__(FTPB) void k_classify(const Tables* __restrict__ T, const Params P, const float* __restrict__ state, int n, int flags,
+__global__ __launch_bounds__(FTPB) void k_classify(const FTables* __restrict__ T, const Params P, const float* __restrict__ state, int n, int flags,
                                                    signed char* __restrict__ cls, int* __restrict__ list, int* __restrict__ count, int cap) {
     const int env = blockIdx.x * FTPB + threadIdx.x;
     if (env >= n) return;
@@ -336,7 +336,7 @@ hipError_t PandaEngine::classify(EnvBuf& b, int cnt, int flags, hipStream_t s) {
     if (!lane_per_env(this)) return hipSuccess;
     hipError_t e = hipMemsetAsync(b.count + b.ccur * NB, 0, NB * sizeof(int), s);
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(k_classify, dim3((cnt + FTPB - 1) / FTPB), dim3(FTPB), 0, s, dT, P, b.state, cnt, flags, b.cls + (size_t)b.cur * b.cap, b.list[b.cur], b.count + b.ccur * NB, b.cap);
+    hipLaunchKernelGGL(k_classify, dim3((cnt + FTPB - 1) / FTPB), dim3(FTPB), 0, s, dFT, P, b.state, cnt, flags, b.cls + (size_t)b.cur * b.cap, b.list[b.cur], b.count + b.ccur * NB, b.cap);
     hipLaunchKernelGGL(k_total, dim3(1), dim3(1), 0, s, b.count + b.ccur * NB, b.h_total, b.count + 3 * NB);
     hipError_t le = hipGetLastError();
     if (le != hipSuccess) return le;
@@ -366,7 +366,7 @@ hipError_t PandaEngine::settle_steps(EnvBuf& b, int cnt, int count, int flags, h
 hipError_t PandaEngine::step_repeat(bool last, const float* d_actions, float* d_rows, int flags, hipStream_t s) {
     if (!P.use_ik)
         return last ? launch_step<MODE_STEP>(this, main, n, d_actions, d_rows, flags, s) : launch_step<MODE_INNER>(this, main, n, d_actions, nullptr, flags, s);
-    hipLaunchKernelGGL(k_ik<false>, dim3((n + FTPB - 1) / FTPB), dim3(FTPB), 0, s, dT, P, main.state, d_actions, main.tgt, n, act_dim);
+    hipLaunchKernelGGL(k_ik<false>, dim3((n + FTPB - 1) / FTPB), dim3(FTPB), 0, s, dFT, P, main.state, d_actions, main.tgt, n, act_dim);
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
     return last ? launch_step<MODE_STEP_IK>(this, main, n, nullptr, d_rows, flags, s) : launch_step<MODE_INNER_IK>(this, main, n, nullptr, nullptr, flags, s);
@@ -376,6 +376,13 @@ void PandaEngine::launch_observe_all(hipStream_t s) {
 }
 void PandaEngine::launch_snapshot_reset(const unsigned char* mask, hipStream_t s) {
     hipLaunchKernelGGL(k_snapshot_reset, dim3((n + 127) / 128), dim3(128), 0, s, dT, P, main.state, mask, n);
+}
+
+// the model constants in both layouts: `Tables` for the row kernels, its per-joint packing for the lane-per-env ones (one source: T)
+hipError_t PandaEngine::upload_tables() {
+    fast_tables(T, FT);
+    const hipError_t e = hipMemcpy(dT, &T, sizeof(Tables), hipMemcpyHostToDevice);
+    return e != hipSuccess ? e : hipMemcpy(dFT, &FT, sizeof(FTables), hipMemcpyHostToDevice);
 }
 
 int PandaEngine::init(const pbre_config& c) {
@@ -410,7 +417,8 @@ int PandaEngine::init(const pbre_config& c) {
         HIPCHK(hipEventCreateWithFlags(ev_join_sys.out(), hipEventDisableTiming));
     }
     HIPCHK(hipMalloc(dT.out(), sizeof(Tables)));
-    HIPCHK(hipMemcpy(dT, &T, sizeof(Tables), hipMemcpyHostToDevice));
+    HIPCHK(hipMalloc(dFT.out(), sizeof(FTables)));
+    HIPCHK(upload_tables());
     HIPCHK(alloc_buf(main, npad));
     HIPCHK(alloc_buf(tmp, npad));
     state = main.state;
@@ -463,7 +471,7 @@ int PandaEngine::reset(const uint8_t* mask) {
         // reset_simulation (panda_push_gym_env.py:117-148): 100 steps robot alone, then world loaded: 100 + 1 steps
         HIPCHK(classify(work, cnt, PBRE_F_NO_OBJECT, stream));
         if (P.use_ik) {     // pandaEnv.reset with use_IK (panda_env.py:83-91): IK targets of the home hand pose + one step
-            hipLaunchKernelGGL(k_ik<true>, dim3((cnt + FTPB - 1) / FTPB), dim3(FTPB), 0, stream, dT, P, work.state, (const float*)nullptr, work.tgt, cnt, act_dim);
+            hipLaunchKernelGGL(k_ik<true>, dim3((cnt + FTPB - 1) / FTPB), dim3(FTPB), 0, stream, dFT, P, work.state, (const float*)nullptr, work.tgt, cnt, act_dim);
             HIPCHK(hipGetLastError());
             HIPCHK(settle_steps(work, cnt, 1, PBRE_F_NO_OBJECT, stream));
         }
@@ -483,7 +491,7 @@ int PandaEngine::reset(const uint8_t* mask) {
             HIPCHK(hipMemcpy(rec, main.state, sizeof rec, hipMemcpyDeviceToHost));
             for (int k = 0; k < NJ; k++) { P.rst_q[k] = rec[k]; T.rst_q[k] = rec[k]; }
             P.rst_objz = rec[11];
-            HIPCHK(hipMemcpy(dT, &T, sizeof(Tables), hipMemcpyHostToDevice));
+            HIPCHK(upload_tables());
             have_snapshot = true; stale_snapshot = false;
             // end-effector pose of the settled robot (the first 6 observation entries of env 0) for the in-kernel restart
             launch_observe_all(stream);

@@ -12,8 +12,8 @@
 // Same mathematics as pbre_core.hpp (world-frame RNEA + CRBA + explicit M^-1, Bullet row order:
 // motors in alternating direction, normals, frictions), same reference call sites.  The kinematic
 // topology is a compile-time template argument so every array index folds and all link data stay in
-// registers; the numeric model constants are read from `Tables` with wave-uniform addresses (scalar
-// loads).  Plain C++: compiled for the device in pbre_capi.hip and for the host in tests/host_emu.
+// registers; the numeric model constants are read from `FastTables` (pbre_tables.hpp: `Tables` packed per
+// joint) with wave-uniform addresses (scalar loads, one per record).  Plain C++: compiled for the device in pbre_capi.hip and for the host in tests/host_emu.
 #pragma once
 #include <math.h>
 #include "pbre_tables.hpp"
@@ -30,6 +30,9 @@
 #endif
 #ifndef PBRE_LAUNDER        // hide a (uniform) pointer's provenance from the optimiser (device build)
 #define PBRE_LAUNDER(p) do {} while (0)
+#endif
+#ifndef PBRE_PIN            // PBRE_LAUNDER that also waits for a per-lane value: the loads through p cannot start before x exists (device build)
+#define PBRE_PIN(p, x) do {} while (0)
 #endif
 #ifndef PBRE_CONST_AS       // device build: the constant address space -- wave-uniform loads from it are scalar loads (s_load), whatever stores
 #define PBRE_CONST_AS       // precede them; nothing on the host.  See step_t's call of finish().
@@ -74,6 +77,53 @@ typedef float pbre_f2 __attribute__((ext_vector_type(2)));
 #endif
 #ifndef PBRE_PAIR_SYNC      // the robot wave of a pair waits for its object wave (device build: pbre_panda.hpp; never reached on the host)
 #define PBRE_PAIR_SYNC(px, ln) do {} while (0)
+#endif
+// Where the lane-per-env code reads the model constants from.  1 (default): FastTables (pbre_tables.hpp) -- one aligned record per joint /
+// sub-body / collision sphere, the spheres sorted by owner link; 0: the lane-SoA `Tables` of the row kernels, the layout this code read before (A/B: the
+// same expressions on the same values, bit-identical results).  Only the source of an operand differs between the two, never an expression.
+#ifndef PBRE_FAST_TABLES
+#define PBRE_FAST_TABLES 1
+#endif
+#if PBRE_FAST_TABLES
+#define PBRE_T_AXIS(T, k, j)     (T).fr[j].axis[k]
+#define PBRE_T_R0(T, k, j)       (T).fr[j].R0[k]
+#define PBRE_T_P0(T, k, j)       (T).fr[j].p0[k]
+#define PBRE_T_SB_M(T, b, j)     (T).sb[j][b].m
+#define PBRE_T_SB_C(T, b, k, j)  (T).sb[j][b].c[k]
+#define PBRE_T_SB_I(T, b, k, j)  (T).sb[j][b].I[k]
+#define PBRE_T_J(T, f, j)        (T).jt[j].f
+#define PBRE_T_SC(T, k, s)       (T).sph[s].c[k]
+#define PBRE_T_SR(T, s)          (T).sph[s].r
+#define PBRE_T_SMU(T, s)         (T).sph[s].mu
+#define PBRE_T_SIDX(T, s)        (T).sph[s].idx       /* the sphere's index in `Tables`: Cand::idx, the tie-break of better() */
+// the collision spheres link j owns, in the order of their `Tables` indices: s is the position in the sorted array
+#define PBRE_T_OWNED(T, j, s)    for (int s = (T).s_begin[j], s##_end_ = (T).s_begin[(j) + 1]; s < s##_end_; s++)
+#else
+#define PBRE_T_AXIS(T, k, j)     (T).axis[k][j]
+#define PBRE_T_R0(T, k, j)       (T).R0[k][j]
+#define PBRE_T_P0(T, k, j)       (T).p0[k][j]
+#define PBRE_T_SB_M(T, b, j)     (T).sb_m[b][j]
+#define PBRE_T_SB_C(T, b, k, j)  (T).sb_c[b][k][j]
+#define PBRE_T_SB_I(T, b, k, j)  (T).sb_I[b][k][j]
+#define PBRE_T_J(T, f, j)        (T).f[j]
+#define PBRE_T_SC(T, k, s)       (T).s_c[k][s]
+#define PBRE_T_SR(T, s)          (T).s_r[s]
+#define PBRE_T_SMU(T, s)         (T).s_mu[s]
+#define PBRE_T_SIDX(T, s)        (s)
+#define PBRE_T_OWNED(T, j, s)    for (int s = 0; s < (T).nspheres; s++) if ((T).s_owner[s] != (j)) continue; else
+#endif
+// Pins the table reads of one joint's part of a sweep to that part: from here to the end of the enclosing block `T` is the same table behind
+// a pointer the optimiser cannot see through, available once the per-lane value x is (something the previous joint computed).  Without it the
+// scheduler starts every joint's record loads at the top of the sweep -- one wide load each now, cheap to hoist -- and 9 x 16 SGPRs are live
+// at once: they spill to VGPR lanes (measured on k_fused: SGPR spills 529 -> 1035, and the VGPR allocation grew; a laundered pointer WITHOUT the
+// value operand -- PBRE_LAUNDER -- still let the loads drift up: 411 spills; with it: 203).  Nothing on the host.
+#ifndef PBRE_PIN_MODE       // 1: as described; 0: no pinning (A/B).  The lane-SoA layout is read as it always was
+#define PBRE_PIN_MODE (PBRE_FAST_TABLES ? 1 : 0)
+#endif
+#if PBRE_PIN_MODE
+#define PBRE_T_PIN(T, x) const auto* T##_pin_ = &(T); PBRE_PIN(T##_pin_, x); const auto& T = *T##_pin_
+#else
+#define PBRE_T_PIN(T, x) do {} while (0)
 #endif
 #include "pbre_objstep.hpp"
 
@@ -126,7 +176,15 @@ inline bool topo_matches(const Tables& T) {
     return true;
 }
 
-typedef PBRE_CONST_AS Tables CTables;
+// FTables: the model constants as the lane-per-env code reads them (PBRE_FAST_TABLES); fast_tables(): that view of a finished `Tables`
+#if PBRE_FAST_TABLES
+typedef FastTables FTables;
+inline void fast_tables(const Tables& T, FTables& F) { pack_fast_tables(T, F); }
+#else
+typedef Tables FTables;
+inline void fast_tables(const Tables& T, FTables& F) { F = T; }
+#endif
+typedef PBRE_CONST_AS FTables CTables;
 
 template <class Topo>
 struct Fast {
@@ -243,9 +301,9 @@ struct Fast {
     template <class TT>
     static PBRE_HD void fk(const TT& T, const float* q, Kin& K) {
         PBRE_UNROLL for (int j = 0; j < ND; j++) {
-            V3 ax = v3(T.axis[0][j], T.axis[1][j], T.axis[2][j]);
-            M3 R0; PBRE_UNROLL for (int k = 0; k < 9; k++) R0.m[k] = T.R0[k][j];
-            V3 p0 = v3(T.p0[0][j], T.p0[1][j], T.p0[2][j]);
+            V3 ax = v3(PBRE_T_AXIS(T, 0, j), PBRE_T_AXIS(T, 1, j), PBRE_T_AXIS(T, 2, j));
+            M3 R0; PBRE_UNROLL for (int k = 0; k < 9; k++) R0.m[k] = PBRE_T_R0(T, k, j);
+            V3 p0 = v3(PBRE_T_P0(T, 0, j), PBRE_T_P0(T, 1, j), PBRE_T_P0(T, 2, j));
             M3 Rl; V3 pl;
             if (Topo::jtype(j) == 1) {
                 float c, s; sincos_(q[j], s, c); const float C = 1.f - c;
@@ -613,7 +671,7 @@ struct Fast {
     // TT: `Tables` or CTables, the same struct in the constant address space (pbre_capi.hip k_fused: there the tables pointer is not a
     // __restrict__ kernel argument every store is known not to alias, and through a plain pointer the model constants came in as per-lane
     // vector loads of a uniform address -- 50 x4 loads whose results were spilled, 488 B of scratch per lane -- instead of scalar loads)
-    template <bool RT = false, class TT = Tables>
+    template <bool RT = false, class TT = FTables>
     static PBRE_HD int step(const TT& T, const Params& P, float* st, const float* act, float* out, int mode, int flags,
                             unsigned long long env_id, const float* tgt, int* sw = nullptr) {
         if (st[46] != 0.f) return skipped(T, P, st, out, mode, flags, env_id);
@@ -621,7 +679,7 @@ struct Fast {
     }
     // action_repeat > 1: the env left the apply_action loop in an earlier iteration of this env.step() (`if self._termination():
     // break`, panda_push_gym_env.py:239-240; flag X[14]): no simulation step, only the evaluation of the state it is in
-    template <class TT = Tables>
+    template <class TT = FTables>
     static PBRE_HD int skipped(const TT& T, const Params& P, float* st, float* out, int mode, int flags, unsigned long long env_id) {
         float q[ND], qd[ND];
         PBRE_UNROLL for (int j = 0; j < ND; j++) { q[j] = st[j]; qd[j] = st[16 + j]; }
@@ -629,7 +687,7 @@ struct Fast {
         Q4 oq; oq.x = st[12]; oq.y = st[13]; oq.z = st[14]; oq.w = st[15];
         return finish(T, P, st, q, qd, op, oq, out, mode, flags, env_id);
     }
-    template <bool RT = false, class TT = Tables>
+    template <bool RT = false, class TT = FTables>
     static PBRE_HD int step_rc(const TT& T, const Params& P, float* st, const float* act, float* out, int mode, int flags,
                                unsigned long long env_id = 0, const float* tgt = nullptr, int* sw = nullptr) {
         if (st[46] != 0.f) return skipped(T, P, st, out, mode, flags, env_id);
@@ -647,7 +705,7 @@ struct Fast {
     // <= P.res_lim.  The test couples the blocks of the simple class, so the motor rows run sequentially next to the object's rows (no
     // closed form, no split over two waves); a lane that has left the loop keeps a snapshot of its velocities while its wave-mates go on
     // (what an env computes does not depend on the lanes it shares a wave with).  The sweeps run are reported through `sw`.
-    template <bool RC, int ROLE = 0, bool RT = false, class TT = Tables>
+    template <bool RC, int ROLE = 0, bool RT = false, class TT = FTables>
     static PBRE_HD int step_t(const TT& T, const Params& P, float* st, const float* act, float* out, int mode, int flags,
                               unsigned long long env_id, const float* tgt, PairX* px = nullptr, int ln = 0, int* sw = nullptr) {
         static_assert(ROLE == 0 || !RC, "the pair kernel steps the simple class");
@@ -692,9 +750,10 @@ struct Fast {
             PBRE_UNROLL for (int j = 0; j < ND; j++) {
                 const int pj = Topo::parent(j) < 0 ? 0 : Topo::parent(j);
                 const bool root = Topo::parent(j) < 0;
-                V3 ax = v3(T.axis[0][j], T.axis[1][j], T.axis[2][j]);
-                M3 R0; PBRE_UNROLL for (int k = 0; k < 9; k++) R0.m[k] = T.R0[k][j];
-                V3 p0 = v3(T.p0[0][j], T.p0[1][j], T.p0[2][j]);
+                PBRE_T_PIN(T, root ? q[j] : p[pj].x);
+                V3 ax = v3(PBRE_T_AXIS(T, 0, j), PBRE_T_AXIS(T, 1, j), PBRE_T_AXIS(T, 2, j));
+                M3 R0; PBRE_UNROLL for (int k = 0; k < 9; k++) R0.m[k] = PBRE_T_R0(T, k, j);
+                V3 p0 = v3(PBRE_T_P0(T, 0, j), PBRE_T_P0(T, 1, j), PBRE_T_P0(T, 2, j));
                 M3 Rl; V3 pl;
                 if (Topo::jtype(j) == 1) {
                     float c, sn; sincos_(q[j], sn, c); const float C = 1.f - c;
@@ -714,18 +773,17 @@ struct Fast {
                 V3 ca = cross(Va[j], sa), cl = add(cross(Va[j], sl), cross(Vl[j], sa));
                 if (root) { Aa[j] = ca; Al[j] = v3(cl.x, cl.y, cl.z - P.gz); } else { Aa[j] = add(Aa[pj], ca); Al[j] = add(Al[pj], cl); }
                 // robot collision spheres owned by this link vs object / table (the simple class has none in range)
-                if (RC) for (int s = 0; s < T.nspheres; s++) {
-                    if (T.s_owner[s] != j) continue;
-                    V3 sc = add(p[j], mv(R[j], v3(T.s_c[0][s], T.s_c[1][s], T.s_c[2][s])));
+                if (RC) PBRE_T_OWNED(T, j, s) {
+                    V3 sc = add(p[j], mv(R[j], v3(PBRE_T_SC(T, 0, s), PBRE_T_SC(T, 1, s), PBRE_T_SC(T, 2, s))));
                     {
-                        Cand c; c.idx = s; c.owner = j;
+                        Cand c; c.idx = PBRE_T_SIDX(T, s); c.owner = j;
                         if (obj_on) {
-                            c.dist = sphere_box(sc, T.s_r[s], op, Ro, oh, c.n, c.pB); c.pA = add(c.pB, scl(c.n, c.dist));
-                            c.mu = T.s_mu[s] * o_mu;
+                            c.dist = sphere_box(sc, PBRE_T_SR(T, s), op, Ro, oh, c.n, c.pB); c.pA = add(c.pB, scl(c.n, c.dist));
+                            c.mu = PBRE_T_SMU(T, s) * o_mu;
                             keepn(c, P.margin, kO);
                         }
-                        c.dist = sphere_box(sc, T.s_r[s], tc, Id, th, c.n, c.pB); c.pA = add(c.pB, scl(c.n, c.dist));
-                        c.mu = T.s_mu[s] * P.tab_mu;
+                        c.dist = sphere_box(sc, PBRE_T_SR(T, s), tc, Id, th, c.n, c.pB); c.pA = add(c.pB, scl(c.n, c.dist));
+                        c.mu = PBRE_T_SMU(T, s) * P.tab_mu;
                         keepn(c, P.margin, kT);
                     }
                 }
@@ -733,10 +791,10 @@ struct Fast {
                 PBRE_UNROLL for (int k = 0; k < 6; k++) CI[j][k] = 0.f;
                 PBRE_UNROLL for (int b = 0; b < NSUB; b++) {
                     if (b >= Topo::nsub(j)) continue;
-                    const float m = T.sb_m[b][j];
-                    V3 c = add(p[j], mv(R[j], v3(T.sb_c[b][0][j], T.sb_c[b][1][j], T.sb_c[b][2][j])));
-                    M3 Il; Il.m[0] = T.sb_I[b][0][j]; Il.m[1] = T.sb_I[b][3][j]; Il.m[2] = T.sb_I[b][4][j];
-                    Il.m[3] = Il.m[1]; Il.m[4] = T.sb_I[b][1][j]; Il.m[5] = T.sb_I[b][5][j]; Il.m[6] = Il.m[2]; Il.m[7] = Il.m[5]; Il.m[8] = T.sb_I[b][2][j];
+                    const float m = PBRE_T_SB_M(T, b, j);
+                    V3 c = add(p[j], mv(R[j], v3(PBRE_T_SB_C(T, b, 0, j), PBRE_T_SB_C(T, b, 1, j), PBRE_T_SB_C(T, b, 2, j))));
+                    M3 Il; Il.m[0] = PBRE_T_SB_I(T, b, 0, j); Il.m[1] = PBRE_T_SB_I(T, b, 3, j); Il.m[2] = PBRE_T_SB_I(T, b, 4, j);
+                    Il.m[3] = Il.m[1]; Il.m[4] = PBRE_T_SB_I(T, b, 1, j); Il.m[5] = PBRE_T_SB_I(T, b, 5, j); Il.m[6] = Il.m[2]; Il.m[7] = Il.m[5]; Il.m[8] = PBRE_T_SB_I(T, b, 2, j);
                     M3 RI = mm(R[j], Il), Iw;
                     PBRE_UNROLL for (int a = 0; a < 3; a++)
                         PBRE_UNROLL for (int bb = 0; bb < 3; bb++)
@@ -815,11 +873,12 @@ struct Fast {
             PBRE_UNROLL for (int k = 0; k < ND; k++) a = fmaf(Mi[sym(j, k)], tau[k], a);
             const float wj = clampf(fmaf(dt, a, qd[j]), -vmax, vmax);
             wset(w, j, wj);
-            float qdes = T.home[j], kp = T.kp_hold[j], kd = T.kd_hold[j];
+            PBRE_T_PIN(T, wj);
+            float qdes = PBRE_T_J(T, home, j), kp = PBRE_T_J(T, kp_hold, j), kd = PBRE_T_J(T, kd_hold, j);
             if (mode & M_TGT) qdes = tgt[j];          // IK mode: all joints track the IK solution with the hold gains (panda_env.py:276-282)
             if (mode & M_ACTION) {
-                kp = T.kp_act[j]; kd = T.kd_act[j];
-                if (j < T.n_act) qdes = clampf(fmaf(act[j], P.act_scale, q[j]), T.lower[j], T.upper[j]);
+                kp = PBRE_T_J(T, kp_act, j); kd = PBRE_T_J(T, kd_act, j);
+                if (j < T.n_act) qdes = clampf(fmaf(act[j], P.act_scale, q[j]), PBRE_T_J(T, lower, j), PBRE_T_J(T, upper, j));
             }
             m_dinv[j] = 1.f / Mi[sym(j, j)];
             m_t[j] = kp * (qdes - q[j]) * inv_dt + (1.f - kd) * wj;      // the motor's target velocity (btMultiBodyJointMotor)
@@ -887,7 +946,7 @@ struct Fast {
         if (RC) {
             bool lim = false;
             PBRE_UNROLL for (int j = 0; j < ND; j++) {
-                const float pl = q[j] - T.lower[j], pu = T.upper[j] - q[j];
+                const float pl = q[j] - PBRE_T_J(T, lower, j), pu = PBRE_T_J(T, upper, j) - q[j];
                 const bool lo_v = pl <= 0.f, up_v = !lo_v && pu <= 0.f;
                 l_dir[j] = lo_v ? 1.f : (up_v ? -1.f : 0.f);
                 const float pen = lo_v ? pl : pu;
@@ -1424,13 +1483,13 @@ struct Fast {
     // normally far from any contact; on the few waves of the complex-env kernels the extra tests would only add latency)
     // ROLE 1 (robot wave of the pair kernel): the new object pose is not known yet -- the sphere centres are parked in LDS and tested
     // against the object by sweep_object() once the object wave has delivered it; cls then only counts the table and the limits.
-    template <int ROLE = 0, class TT = Tables>
+    template <int ROLE = 0, class TT = FTables>
     static PBRE_HD Tail sweep(const TT& T, const Params& P, const float* q, const float* qd, V3 op, Q4 oq, int flags, bool bounds = false,
                               PairX* px = nullptr, int ln = 0) {
         const bool obj_on = !(flags & 1);
         Tail t;
         bool lim = false;
-        PBRE_UNROLL for (int j = 0; j < ND; j++) lim = lim || (q[j] - T.lower[j] <= 0.f) || (T.upper[j] - q[j] <= 0.f);
+        PBRE_UNROLL for (int j = 0; j < ND; j++) lim = lim || (q[j] - PBRE_T_J(T, lower, j) <= 0.f) || (PBRE_T_J(T, upper, j) - q[j] <= 0.f);
         const M3 Ro = quat_R(oq);
         const V3 oh = v3(P.obj_h[0], P.obj_h[1], P.obj_h[2]);
         const V3 tc = v3(P.tab_c[0], P.tab_c[1], P.tab_c[2]), th = v3(P.tab_h[0], P.tab_h[1], P.tab_h[2]);
@@ -1445,9 +1504,10 @@ struct Fast {
         float pr0 = 0.f, pr1 = 0.f;
         PBRE_UNROLL for (int j = 0; j < ND; j++) {
             const int pj = Topo::parent(j) < 0 ? 0 : Topo::parent(j);
-            V3 ax = v3(T.axis[0][j], T.axis[1][j], T.axis[2][j]);
-            M3 R0; PBRE_UNROLL for (int k = 0; k < 9; k++) R0.m[k] = T.R0[k][j];
-            V3 p0 = v3(T.p0[0][j], T.p0[1][j], T.p0[2][j]);
+            PBRE_T_PIN(T, Topo::parent(j) < 0 ? q[j] : p[pj].x);
+            V3 ax = v3(PBRE_T_AXIS(T, 0, j), PBRE_T_AXIS(T, 1, j), PBRE_T_AXIS(T, 2, j));
+            M3 R0; PBRE_UNROLL for (int k = 0; k < 9; k++) R0.m[k] = PBRE_T_R0(T, k, j);
+            V3 p0 = v3(PBRE_T_P0(T, 0, j), PBRE_T_P0(T, 1, j), PBRE_T_P0(T, 2, j));
             M3 Rl; V3 pl;
             if (Topo::jtype(j) == 1) {
                 float c, sn; sincos_(q[j], sn, c); const float C = 1.f - c;
@@ -1460,14 +1520,13 @@ struct Fast {
                 Rl = R0; V3 d = mv(R0, ax); pl = v3(fmaf(d.x, q[j], p0.x), fmaf(d.y, q[j], p0.y), fmaf(d.z, q[j], p0.z));
             }
             if (Topo::parent(j) < 0) { R[j] = Rl; p[j] = pl; } else { R[j] = mm(R[pj], Rl); p[j] = add(p[pj], mv(R[pj], pl)); }
-            for (int s = 0; s < T.nspheres; s++) {
-                if (T.s_owner[s] != j) continue;
-                V3 sc = add(p[j], mv(R[j], v3(T.s_c[0][s], T.s_c[1][s], T.s_c[2][s])));
+            PBRE_T_OWNED(T, j, s) {
+                V3 sc = add(p[j], mv(R[j], v3(PBRE_T_SC(T, 0, s), PBRE_T_SC(T, 1, s), PBRE_T_SC(T, 2, s))));
                 // cheap lower bounds on the two distances first (bounding sphere of the object; height above the table top); the
                 // exact sphere-box tests (a square root each) only run if some lane of the wave is not clearly far
-                const float sr = T.s_r[s];
+                const float sr = PBRE_T_SR(T, s);
                 if (ROLE == 1) { px->sc[3 * s][ln] = sc.x; px->sc[3 * s + 1][ln] = sc.y; px->sc[3 * s + 2][ln] = sc.z; }
-                else if (ROLE == 3) {      // row wave: lane s mod 16 of the group keeps sphere s, the tests follow the loop -- one pass for all spheres
+                else if (ROLE == 3) {      // row wave: lane s mod 16 of the group keeps sphere s (s: its place in the table this loop walks), the tests follow the loop -- one pass for all spheres
                     const bool mine = (s & 15) == ln;
                     if (s < 16) { if (mine) { pk0 = sc; pr0 = sr; } } else if (mine) { pk1 = sc; pr1 = sr; }
                     continue;
@@ -1507,6 +1566,7 @@ struct Fast {
         return t;
     }
     // the object half of sweep<1>'s classification: the parked sphere centres against the object pose (same tests, same operands)
+    // (slot s of PairX::sc is sphere s of the table sweep<1> walked -- the same table, so the same order, here; the count does not depend on it)
     template <class TT>
     static PBRE_HD int sweep_object(const TT& T, const Params& P, V3 op, Q4 oq, bool bounds, const PairX* px, int ln) {
         const M3 Ro = quat_R(oq);
@@ -1515,7 +1575,7 @@ struct Fast {
         int nO = 0;
         for (int s = 0; s < T.nspheres; s++) {
             const V3 sc = v3(px->sc[3 * s][ln], px->sc[3 * s + 1][ln], px->sc[3 * s + 2][ln]);
-            const float sr = T.s_r[s];
+            const float sr = PBRE_T_SR(T, s);
             const V3 dd = sub(sc, op);
             const float reach = sr + P.margin + orad;
             if ((!bounds || PBRE_ANY(!(dot(dd, dd) >= reach * reach))) && sphere_obj_dist(P, sc, sr, op, Ro, oh) < P.margin) nO++;
@@ -1523,7 +1583,7 @@ struct Fast {
         return nO;
     }
     // class of the state stored in `st` (after reset / set_state)
-    static PBRE_HD int classify_state(const Tables& T, const Params& P, const float* st, int flags) {
+    static PBRE_HD int classify_state(const FTables& T, const Params& P, const float* st, int flags) {
         float q[ND];
         PBRE_UNROLL for (int j = 0; j < ND; j++) q[j] = st[j];
         Q4 oq; oq.x = st[12]; oq.y = st[13]; oq.z = st[14]; oq.w = st[15];
@@ -1545,7 +1605,7 @@ struct Fast {
     // Damped-least-squares IK of the end effector from the current joint angles (replaces p.calculateInverseKinematics,
     // reference panda_env.py:269-272: maxNumIterations=100, residualThreshold=1e-3); same algorithm as oracle/orc_ik:
     // e = [p_t - p_ee ; rotvec(R_t R_ee^T)], dq = J^T (J J^T + lambda^2 I)^-1 e on the joints of the EE chain, until |e_pos| < res.
-    static PBRE_HD void ik_solve(const Tables& T, const Params& P, const float* q0, V3 pos, V3 eul, float* q) {
+    static PBRE_HD void ik_solve(const FTables& T, const Params& P, const float* q0, V3 pos, V3 eul, float* q) {
         const M3 Rt = quat_R(euler_quat(eul));
         PBRE_UNROLL for (int j = 0; j < ND; j++) q[j] = q0[j];
         const int eo = T.ee_owner;
@@ -1557,9 +1617,9 @@ struct Fast {
             M3 Re = Eo; V3 po = v3(0.f, 0.f, 0.f);
             PBRE_UNROLL for (int j = 0; j < ND; j++) {
                 const int pj = Topo::parent(j) < 0 ? 0 : Topo::parent(j);
-                V3 ax = v3(T.axis[0][j], T.axis[1][j], T.axis[2][j]);
-                M3 R0; PBRE_UNROLL for (int k = 0; k < 9; k++) R0.m[k] = T.R0[k][j];
-                V3 p0 = v3(T.p0[0][j], T.p0[1][j], T.p0[2][j]);
+                V3 ax = v3(PBRE_T_AXIS(T, 0, j), PBRE_T_AXIS(T, 1, j), PBRE_T_AXIS(T, 2, j));
+                M3 R0; PBRE_UNROLL for (int k = 0; k < 9; k++) R0.m[k] = PBRE_T_R0(T, k, j);
+                V3 p0 = v3(PBRE_T_P0(T, 0, j), PBRE_T_P0(T, 1, j), PBRE_T_P0(T, 2, j));
                 M3 Rl; V3 pl;
                 if (Topo::jtype(j) == 1) {
                     float c, sn; sincos_(q[j], sn, c); const float C = 1.f - c;
@@ -1632,7 +1692,7 @@ struct Fast {
     // apply_action, IK branch (panda_push_gym_env.py:197-222 + panda_env.py:229-291): accumulate the scaled Cartesian action into
     // the hand pose, clip it to the rotation limits and the robot workspace, solve IK, store the joint targets.
     // reset = true: pandaEnv.reset with use_IK (panda_env.py:83-91): targets of the home hand pose.
-    static PBRE_HD void ik_targets(const Tables& T, const Params& P, float* st, const float* act, float* tgt, bool reset) {
+    static PBRE_HD void ik_targets(const FTables& T, const Params& P, float* st, const float* act, float* tgt, bool reset) {
         float hp[6];
         if (reset) { PBRE_UNROLL for (int k = 0; k < 6; k++) hp[k] = P.home_hand[k]; }
         else {
@@ -1667,7 +1727,7 @@ struct Fast {
     // opaque pointer, so the compiler issued them as per-lane FLAT loads of a uniform address -- ~200 vector loads with a full memory
     // round trip each, 45 k of the robot wave's 138 k cycles on a lone wave (tools/phase_probe.py) -- and even the `owner == link` scan
     // over the collision spheres ran on vector compares.  From the constant address space they are scalar loads again.
-    template <int ROLE = 0, class TT = Tables>
+    template <int ROLE = 0, class TT = FTables>
     static PBRE_HD int finish(const TT& T, const Params& P, float* st, float* q, float* qd, V3 op, Q4 oq,
                               float* out, int mode, int flags, unsigned long long env_id, bool bounds = false, PairX* px = nullptr, int ln = 0) {
         const bool want_obs = (mode & (M_OBS | M_TASK)) != 0;
@@ -1813,6 +1873,35 @@ struct Fast {
         if constexpr (ROLE != 1) cls = rt_class(P, st, flags, cls);
         return cls | (bad ? BAD_BIT : 0);
     }
+
+#if PBRE_FAST_TABLES && !defined(__HIPCC__)
+    // Host callers that hold the lane-SoA `Tables` only (the host emulation, tests/host_emu): the same entry points taking `Tables`, which pack it
+    // for the call and run the code above on the packed view -- so the emulation executes exactly what the device executes.  (Host only: the
+    // device engine packs once per upload, PandaEngine::upload_tables.)
+    static FTables packed(const Tables& T) { FTables F; fast_tables(T, F); return F; }
+    template <bool RT = false>
+    static int step(const Tables& T, const Params& P, float* st, const float* act, float* out, int mode, int flags,
+                    unsigned long long env_id, const float* tgt, int* sw = nullptr) {
+        return step<RT, FTables>(packed(T), P, st, act, out, mode, flags, env_id, tgt, sw);
+    }
+    template <bool RT = false>
+    static int step_rc(const Tables& T, const Params& P, float* st, const float* act, float* out, int mode, int flags,
+                       unsigned long long env_id = 0, const float* tgt = nullptr, int* sw = nullptr) {
+        return step_rc<RT, FTables>(packed(T), P, st, act, out, mode, flags, env_id, tgt, sw);
+    }
+    template <bool RC, int ROLE = 0, bool RT = false>
+    static int step_t(const Tables& T, const Params& P, float* st, const float* act, float* out, int mode, int flags,
+                      unsigned long long env_id, const float* tgt, PairX* px = nullptr, int ln = 0, int* sw = nullptr) {
+        return step_t<RC, ROLE, RT, FTables>(packed(T), P, st, act, out, mode, flags, env_id, tgt, px, ln, sw);
+    }
+    template <int ROLE = 0>
+    static int finish(const Tables& T, const Params& P, float* st, float* q, float* qd, V3 op, Q4 oq,
+                      float* out, int mode, int flags, unsigned long long env_id, bool bounds = false, PairX* px = nullptr, int ln = 0) {
+        return finish<ROLE, FTables>(packed(T), P, st, q, qd, op, oq, out, mode, flags, env_id, bounds, px, ln);
+    }
+    static int classify_state(const Tables& T, const Params& P, const float* st, int flags) { return classify_state(packed(T), P, st, flags); }
+    static void ik_targets(const Tables& T, const Params& P, float* st, const float* act, float* tgt, bool reset) { ik_targets(packed(T), P, st, act, tgt, reset); }
+#endif
 };
 
 }  // namespace pbre

@@ -16,6 +16,7 @@
 #define PBRE_ANY(x) (__any((int)(x)) != 0)
 #define PBRE_REG_BARRIER() asm volatile("" ::: "memory")
 #define PBRE_LAUNDER(p) asm volatile("" : "+s"(p))
+#define PBRE_PIN(p, x) asm volatile("" : "+s"(p) : "v"(x))
 #define PBRE_PAIR_G_FLAGS (55 * 64 * 4 + 64)       /* byte offset of the 64 sequence words in a tail pair's global record: behind a whole PairX */
 #define PBRE_PAIR_G_BYTES (PBRE_PAIR_G_FLAGS + 64 * 4)
 // (Fast::finish, robot wave of a pair: the object wave's seven values in px->o.  px->g == nullptr: the object wave is a sibling wave of the block --
@@ -158,7 +159,7 @@ __device__ __forceinline__ void publish_class(int env, int c, signed char* __res
 // CT: read the model constants through the constant address space (see Fast::step; measured first in k_fused -- 131072 envs fresh 0.101 ->
 // 0.089 ms -- then made the default of every lane-per-env step kernel; false: A/B)
 template <int MODE, bool RT, bool CT = true>
-__device__ __forceinline__ void fast_wave(const Tables* __restrict__ T, const Params& P, float* __restrict__ state,
+__device__ __forceinline__ void fast_wave(const FTables* __restrict__ T, const Params& P, float* __restrict__ state,
                                           const float* __restrict__ actions, float* __restrict__ out, int n, int act_dim, int ow, int flags,
                                           const signed char* __restrict__ cls_cur, signed char* __restrict__ cls, int* __restrict__ next_list,
                                           int* __restrict__ next_count, int cap, const float* __restrict__ tgt, int* __restrict__ zero_count, int chunk, int ln) {
@@ -217,7 +218,7 @@ __device__ __forceinline__ void fast_wave(const Tables* __restrict__ T, const Pa
     publish_class(env, c, cls, next_list, next_count, cap, P.bad_count);
 }
 template <int MODE, int WPS = PBRE_FAST_WAVES, bool RT = false>
-__global__ __launch_bounds__(FTPB, WPS) void k_fast(const Tables* __restrict__ T, const Params P, float* __restrict__ state,
+__global__ __launch_bounds__(FTPB, WPS) void k_fast(const FTables* __restrict__ T, const Params P, float* __restrict__ state,
                                                const float* __restrict__ actions, float* __restrict__ out, int n, int act_dim, int ow, int flags,
                                                const signed char* __restrict__ cls_cur, signed char* __restrict__ cls, int* __restrict__ next_list,
                                                int* __restrict__ next_count, int cap, const float* __restrict__ tgt, int* __restrict__ zero_count) {
@@ -236,7 +237,7 @@ constexpr int PTPB = 2 * FTPB;
 // (pair_wave: one wave's work -- role 0 the robots, role 1 the objects of the 64 envs of `chunk`, exchange record px; k_fast_pair's body and,
 // round 5, the simple envs' part of k_fused<.., true>.  One block barrier per wave that has a simulating lane.)
 template <int MODE, bool CT = true>
-__device__ __forceinline__ void pair_wave(const Tables* __restrict__ T, const Params& P, float* __restrict__ state,
+__device__ __forceinline__ void pair_wave(const FTables* __restrict__ T, const Params& P, float* __restrict__ state,
                                           const float* __restrict__ actions, float* __restrict__ out, int n, int act_dim, int ow, int flags,
                                           const signed char* __restrict__ cls_cur, signed char* __restrict__ cls, int* __restrict__ next_list,
                                           int* __restrict__ next_count, int cap, const float* __restrict__ tgt, int* __restrict__ zero_count,
@@ -276,7 +277,7 @@ __device__ __forceinline__ void pair_wave(const Tables* __restrict__ T, const Pa
 #define PBRE_PAIR_WPS 2            // waves per SIMD k_fast_pair is register-limited to (A/B: tools/build_variant.sh)
 #endif
 template <int MODE>
-__global__ __launch_bounds__(PTPB, PBRE_PAIR_WPS) void k_fast_pair(const Tables* __restrict__ T, const Params P, float* __restrict__ state,
+__global__ __launch_bounds__(PTPB, PBRE_PAIR_WPS) void k_fast_pair(const FTables* __restrict__ T, const Params P, float* __restrict__ state,
                                                const float* __restrict__ actions, float* __restrict__ out, int n, int act_dim, int ow, int flags,
                                                const signed char* __restrict__ cls_cur, signed char* __restrict__ cls, int* __restrict__ next_list,
                                                int* __restrict__ next_count, int cap, const float* __restrict__ tgt, int* __restrict__ zero_count) {
@@ -301,7 +302,7 @@ static __device__ __forceinline__ void report_hint(int total, int* __restrict__ 
 }
 
 template <int MODE, bool RT = false>
-__global__ __launch_bounds__(FTPB) void k_fast_rc(const Tables* __restrict__ T, const Params P, float* __restrict__ state,
+__global__ __launch_bounds__(FTPB) void k_fast_rc(const FTables* __restrict__ T, const Params P, float* __restrict__ state,
                                                   const float* __restrict__ actions, float* __restrict__ out, int act_dim, int ow, int flags,
                                                   const int* __restrict__ cur_list, const int* __restrict__ cur_count,
                                                   signed char* __restrict__ cls, int* __restrict__ next_list, int* __restrict__ next_count, int cap,
@@ -347,7 +348,7 @@ constexpr int RTPB = REPB * W + FTPB;
 // twists travel through the per-env global records objv_g[env][W], whose first word the object wave sets to P.objv_seq last (release); no
 // barrier anywhere.  The object wave waits for nothing, and its block is dispatched before its row waves' blocks: the row waves' wait ends.)
 template <int MODE, bool RT, bool G = false>
-__device__ __forceinline__ void row_list_block(const Tables* __restrict__ T, const Params& P, float* __restrict__ state,
+__device__ __forceinline__ void row_list_block(const Tables* __restrict__ T, const FTables* __restrict__ FT, const Params& P, float* __restrict__ state,
                                                const float* __restrict__ actions, float* __restrict__ out, int act_dim, int ow, int flags,
                                                const int* __restrict__ cur_list, const int* __restrict__ cur_count,
                                                signed char* __restrict__ cls, int* __restrict__ next_list, int* __restrict__ next_count, int cap,
@@ -418,7 +419,7 @@ __device__ __forceinline__ void row_list_block(const Tables* __restrict__ T, con
                 FastD::V3 op; op.x = st[9]; op.y = st[10]; op.z = st[11];
                 FastD::Q4 oq; oq.x = st[12]; oq.y = st[13]; oq.z = st[14]; oq.w = st[15];
                 // (the tables through the constant address space: scalar loads although the row's stores precede them -- Fast::finish)
-                const int c = FastD::finish<PBRE_ROW_FINISH16 ? 3 : 0>(*(const CTables*)T, P, st, q, qd, op, oq, (MODE & FastD::M_OBS) ? out + (size_t)env * ow : nullptr, MODE, flags,
+                const int c = FastD::finish<PBRE_ROW_FINISH16 ? 3 : 0>(*(const CTables*)FT, P, st, q, qd, op, oq, (MODE & FastD::M_OBS) ? out + (size_t)env * ow : nullptr, MODE, flags,
                                             P.env_id_base + (unsigned long long)env, false, nullptr, vt & 15);
                 if ((vt & 15) == 0) publish_class(env, c, cls, next_list, next_count, cap, P.bad_count);
             }
@@ -428,13 +429,13 @@ __device__ __forceinline__ void row_list_block(const Tables* __restrict__ T, con
     }
 }
 template <int MODE, bool RT = false>
-__global__ __launch_bounds__(RTPB, 2) void k_row_list(const Tables* __restrict__ T, const Params P, float* __restrict__ state,
+__global__ __launch_bounds__(RTPB, 2) void k_row_list(const Tables* __restrict__ T, const FTables* __restrict__ FT, const Params P, float* __restrict__ state,
                                                   const float* __restrict__ actions, float* __restrict__ out, int act_dim, int ow, int flags,
                                                   const int* __restrict__ cur_list, const int* __restrict__ cur_count,
                                                   signed char* __restrict__ cls, int* __restrict__ next_list, int* __restrict__ next_count, int cap,
                                                   const float* __restrict__ tgt, int* __restrict__ host_total, int dummy_base, int* __restrict__ recent) {
     __shared__ float objv[REPB][W];
-    row_list_block<MODE, RT>(T, P, state, actions, out, act_dim, ow, flags, cur_list, cur_count, cls, next_list, next_count, cap, tgt, host_total, dummy_base, recent,
+    row_list_block<MODE, RT>(T, FT, P, state, actions, out, act_dim, ow, flags, cur_list, cur_count, cls, next_list, next_count, cap, tgt, host_total, dummy_base, recent,
                              objv, (int)blockIdx.x, (int)gridDim.x, (int)threadIdx.x);
 }
 
@@ -468,7 +469,7 @@ struct FusedArgs {
 // instantiation of its own, launched only for steps that will have displaced chunks; a step without complex envs runs the kernel of before.  As a non-inlined FUNCTION
 // the pair's wave cost the kernel 656 B of scratch per lane for the call ABI and crashed on the device: dropped.)
 template <int MODE>
-__device__ __forceinline__ void tail_pair_role(const FusedArgs PBRE_CONST_AS* a, const Tables* __restrict__ T, int tchunk, int role, int ln) {
+__device__ __forceinline__ void tail_pair_role(const FusedArgs PBRE_CONST_AS* a, const FTables* __restrict__ T, int tchunk, int role, int ln) {
     float* pg = (float*)((char*)a->pair_g + (size_t)tchunk * PBRE_PAIR_G_BYTES);
     const int seq = a->P.objv_seq;
     PBRE_LAUNDER(a);
@@ -479,11 +480,11 @@ __device__ __forceinline__ void tail_pair_role(const FusedArgs PBRE_CONST_AS* a,
 // over all of its rows); the row blocks' object waves idle (Core::step<RT> sweeps the object's rows itself).
 // TAIL: the instantiation with tail pairs (64-thread grid, no residual exit), see tail_pair_role
 template <int MODE, bool PAIR, bool RT = false, bool TAIL = false>
-__global__ __launch_bounds__(PAIR ? RTPB : FTPB, 2) void k_fused(const FusedArgs args_in_kernarg_segment, const Tables* __restrict__ T) {
+__global__ __launch_bounds__(PAIR ? RTPB : FTPB, 2) void k_fused(const FusedArgs args_in_kernarg_segment, const Tables* __restrict__ T, const FTables* __restrict__ FT) {
     static_assert(!(PAIR && RT), "the residual exit steps an env on one lane");
     static_assert(!TAIL || (!PAIR && !RT), "tail pairs: the 64-thread grid of the default step");
-    // (T -- the model constants -- is a kernel argument of its own: as a __restrict__ argument it cannot alias the pointers the roles load from the
-    // struct, so the reads through it stay scalar loads behind the roles' stores; read from the struct, 50 of k_fast's s_load_dwordx16 / x8 table
+    // (T and FT -- the model constants, lane-SoA for the row roles' Core::step and packed per joint for the lane-per-env code -- are kernel arguments of their own: as a __restrict__ argument it cannot alias the pointers the roles load from the
+    // struct, so the reads through them stay scalar loads behind the roles' stores; read from the struct, 50 of k_fast's s_load_dwordx16 / x8 table
     // reads had become per-lane global loads and the fast role spilled 488 bytes per lane)
     const FusedArgs PBRE_CONST_AS* a = (const FusedArgs PBRE_CONST_AS*)__builtin_amdgcn_kernarg_segment_ptr();      // (explicit arguments start at offset 0)
     if constexpr (PAIR) {
@@ -491,7 +492,7 @@ __global__ __launch_bounds__(PAIR ? RTPB : FTPB, 2) void k_fused(const FusedArgs
         if ((int)blockIdx.x < a->rblocks) {
             __shared__ float objv[REPB][W];
             PBRE_LAUNDER(a);
-            row_list_block<MODE, false>(T, *(const Params*)&a->P, a->state, a->actions, a->out, a->act_dim, a->ow, a->flags, a->cur_list, a->cur_count, a->cls,
+            row_list_block<MODE, false>(T, FT, *(const Params*)&a->P, a->state, a->actions, a->out, a->act_dim, a->ow, a->flags, a->cur_list, a->cur_count, a->cls,
                                         a->next_list, a->next_count, a->cap, a->tgt, a->host_total, a->dummy_base, a->recent, objv, (int)blockIdx.x, a->rblocks,
                                         (int)threadIdx.x);
             return;
@@ -499,7 +500,7 @@ __global__ __launch_bounds__(PAIR ? RTPB : FTPB, 2) void k_fused(const FusedArgs
         const int fb = (int)blockIdx.x - a->rblocks, wv = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)), ln = (int)(threadIdx.x & (FTPB - 1));
         PBRE_LAUNDER(a);
         __shared__ PairX px[FUSED_WAVES / 2];
-        pair_wave<MODE, true>(T, *(const Params*)&a->P, a->state, a->actions, a->out, a->n, a->act_dim, a->ow, a->flags, a->cls_cur, a->cls, a->next_list, a->next_count, a->cap,
+        pair_wave<MODE, true>(FT, *(const Params*)&a->P, a->state, a->actions, a->out, a->n, a->act_dim, a->ow, a->flags, a->cls_cur, a->cls, a->next_list, a->next_count, a->cap,
                         a->tgt, a->zero_count, px[wv >> 1], fb * (FUSED_WAVES / 2) + (wv >> 1), ln, wv & 1);
     } else {
         // 64-thread blocks, like k_fast's: beside a machine-filling batch (131072 envs = 2048 waves = every wave slot) the row waves displace some
@@ -510,7 +511,7 @@ __global__ __launch_bounds__(PAIR ? RTPB : FTPB, 2) void k_fused(const FusedArgs
         if ((int)blockIdx.x < rb) {
             const int role = (int)blockIdx.x & (FUSED_WAVES - 1);
             PBRE_LAUNDER(a);
-            row_list_block<MODE, RT, true>(T, *(const Params*)&a->P, a->state, a->actions, a->out, a->act_dim, a->ow, a->flags, a->cur_list, a->cur_count, a->cls,
+            row_list_block<MODE, RT, true>(T, FT, *(const Params*)&a->P, a->state, a->actions, a->out, a->act_dim, a->ow, a->flags, a->cur_list, a->cur_count, a->cls,
                                               a->next_list, a->next_count, a->cap, a->tgt, a->host_total, a->dummy_base, a->recent, nullptr,
                                               (int)blockIdx.x / FUSED_WAVES, a->rblocks, (role == 0 ? REPB * W : (role - 1) * FTPB) + (int)threadIdx.x, a->objv_g);
             return;
@@ -526,12 +527,12 @@ __global__ __launch_bounds__(PAIR ? RTPB : FTPB, 2) void k_fused(const FusedArgs
             const int nfast = (a->n + FTPB - 1) / FTPB - a->ntail;
             if (chunk >= nfast) {
                 const int t = chunk - nfast;
-                tail_pair_role<MODE>(a, T, nfast + (t >> 1), (t & 1) ^ 1, (int)threadIdx.x);      // even t: the object wave (dispatched first)
+                tail_pair_role<MODE>(a, FT, nfast + (t >> 1), (t & 1) ^ 1, (int)threadIdx.x);      // even t: the object wave (dispatched first)
                 return;
             }
         }
         PBRE_LAUNDER(a);
-        fast_wave<MODE, RT, true>(T, *(const Params*)&a->P, a->state, a->actions, a->out, a->n, a->act_dim, a->ow, a->flags, a->cls_cur, a->cls, a->next_list, a->next_count,
+        fast_wave<MODE, RT, true>(FT, *(const Params*)&a->P, a->state, a->actions, a->out, a->n, a->act_dim, a->ow, a->flags, a->cls_cur, a->cls, a->next_list, a->next_count,
                                a->cap, a->tgt, a->zero_count, chunk, (int)threadIdx.x);
     }
 }
@@ -558,6 +559,9 @@ struct PandaEngine : pbre_ctx {
     Tables T;
     int npad = 0;
     DevBuf<Tables> dT;
+    FTables FT;                        // T as the lane-per-env code reads it (Fast: FastTables, PBRE_FAST_TABLES); refreshed with every upload of T
+    DevBuf<FTables> dFT;
+    hipError_t upload_tables();        // T -> FT, both to the device
     EnvBuf main, tmp;
     DevBuf<float> d_scratch;
     bool fast_ok = false;
@@ -682,7 +686,7 @@ hipError_t launch_step_t(PandaEngine* c, EnvBuf& b, int n, const float* act, flo
             if (pair) {
                 c->launches_pair++;
                 if constexpr (!RT)      // (`pair` is never set with the residual exit)
-                hipLaunchKernelGGL((k_fused<MODE, true>), dim3(rblocks + (blocks + FUSED_WAVES / 2 - 1) / (FUSED_WAVES / 2)), dim3(RTPB), 0, s, fa, (const Tables*)c->dT);
+                hipLaunchKernelGGL((k_fused<MODE, true>), dim3(rblocks + (blocks + FUSED_WAVES / 2 - 1) / (FUSED_WAVES / 2)), dim3(RTPB), 0, s, fa, (const Tables*)c->dT, (const FTables*)c->dFT);
             } else {
                 // (never 0: that value selects the block barrier, PBRE_OBJV_SYNC.  After 2^31 - 1 launches -- four days of stepping -- the numbers
                 // start over, behind a clear of the records: a record last written 2^31 launches ago must not look complete)
@@ -706,10 +710,10 @@ hipError_t launch_step_t(PandaEngine* c, EnvBuf& b, int n, const float* act, flo
                 if (ntail) c->launches_tail++;
                 bool launched = false;
                 if constexpr (!RT) if (ntail) {
-                    hipLaunchKernelGGL((k_fused<MODE, false, false, true>), dim3(FUSED_WAVES * rblocks + blocks + ntail), dim3(FTPB), 0, s, fa, (const Tables*)c->dT);
+                    hipLaunchKernelGGL((k_fused<MODE, false, false, true>), dim3(FUSED_WAVES * rblocks + blocks + ntail), dim3(FTPB), 0, s, fa, (const Tables*)c->dT, (const FTables*)c->dFT);
                     launched = true;
                 }
-                if (!launched) hipLaunchKernelGGL((k_fused<MODE, false, RT>), dim3(FUSED_WAVES * rblocks + blocks), dim3(FTPB), 0, s, fa, (const Tables*)c->dT);
+                if (!launched) hipLaunchKernelGGL((k_fused<MODE, false, RT>), dim3(FUSED_WAVES * rblocks + blocks), dim3(FTPB), 0, s, fa, (const Tables*)c->dT, (const FTables*)c->dFT);
             }
             if ((e = hipGetLastError()) != hipSuccess) return e;
             if (timed) { (void)hipEventRecord(ek[1], s); c->k_steps++; }
@@ -729,12 +733,12 @@ hipError_t launch_step_t(PandaEngine* c, EnvBuf& b, int n, const float* act, flo
     }
     if constexpr (NB <= 2) {
         if (rows) {
-            hipLaunchKernelGGL((k_row_list<MODE, RT>), dim3(rblocks), dim3(RTPB), 0, s_rc, c->dT, Pk, b.state, act, out, c->act_dim, c->ow, flags,
+            hipLaunchKernelGGL((k_row_list<MODE, RT>), dim3(rblocks), dim3(RTPB), 0, s_rc, c->dT, c->dFT, Pk, b.state, act, out, c->act_dim, c->ow, flags,
                                b.list[cur], b.count + cc * NB, b.cls + (size_t)nxt * b.cap, b.list[nxt], b.count + cn * NB, b.cap, b.tgt, b.h_total, b.cap, b.count + 3 * NB);
         }
     }
     if (!rows)
-        hipLaunchKernelGGL((k_fast_rc<MODE, RT>), dim3(std::min(c->n_simd, blocks + NB)), dim3(FTPB), 0, s_rc, c->dT, Pk, b.state, act, out, c->act_dim, c->ow, flags,
+        hipLaunchKernelGGL((k_fast_rc<MODE, RT>), dim3(std::min(c->n_simd, blocks + NB)), dim3(FTPB), 0, s_rc, c->dFT, Pk, b.state, act, out, c->act_dim, c->ow, flags,
                            b.list[cur], b.count + cc * NB, b.cls + (size_t)nxt * b.cap, b.list[nxt], b.count + cn * NB, b.cap, b.tgt, b.h_total, b.count + 3 * NB);
     if ((e = hipGetLastError()) != hipSuccess) return e;
     // HIP event pair around the dominant kernel on the stream it runs on, for pbre_timing[3]; sampled (every KSAMPLE-th step):
@@ -753,15 +757,15 @@ hipError_t launch_step_t(PandaEngine* c, EnvBuf& b, int n, const float* act, flo
     if (pair) {
         c->launches_pair++;
         if constexpr (!(MODE & FastD::M_INNER) && !RT)      // (the inner iterations of action_repeat > 1 stay on k_fast: not instantiated; RT: one lane per env)
-        hipLaunchKernelGGL((k_fast_pair<MODE>), dim3(blocks), dim3(PTPB), 0, s_fast, c->dT, Pk, b.state, act, out, n, c->act_dim, c->ow, flags,
+        hipLaunchKernelGGL((k_fast_pair<MODE>), dim3(blocks), dim3(PTPB), 0, s_fast, c->dFT, Pk, b.state, act, out, n, c->act_dim, c->ow, flags,
                            b.cls + (size_t)cur * b.cap, b.cls + (size_t)nxt * b.cap, b.list[nxt], b.count + cn * NB, b.cap, b.tgt, b.count + cz * NB);
     } else {
     if (fast3) c->launches3++;
     if constexpr (!RT) if (fast3)
-        hipLaunchKernelGGL((k_fast<MODE, 3, RT>), dim3(blocks), dim3(FTPB), 0, s_fast, c->dT, Pk, b.state, act, out, n, c->act_dim, c->ow, flags,
+        hipLaunchKernelGGL((k_fast<MODE, 3, RT>), dim3(blocks), dim3(FTPB), 0, s_fast, c->dFT, Pk, b.state, act, out, n, c->act_dim, c->ow, flags,
                            b.cls + (size_t)cur * b.cap, b.cls + (size_t)nxt * b.cap, b.list[nxt], b.count + cn * NB, b.cap, b.tgt, b.count + cz * NB);
     if (!fast3)
-        hipLaunchKernelGGL((k_fast<MODE, 2, RT>), dim3(blocks), dim3(FTPB), 0, s_fast, c->dT, Pk, b.state, act, out, n, c->act_dim, c->ow, flags,
+        hipLaunchKernelGGL((k_fast<MODE, 2, RT>), dim3(blocks), dim3(FTPB), 0, s_fast, c->dFT, Pk, b.state, act, out, n, c->act_dim, c->ow, flags,
                            b.cls + (size_t)cur * b.cap, b.cls + (size_t)nxt * b.cap, b.list[nxt], b.count + cn * NB, b.cap, b.tgt, b.count + cz * NB);
     }
     if ((e = hipGetLastError()) != hipSuccess) return e;

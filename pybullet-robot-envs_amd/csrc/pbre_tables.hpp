@@ -88,6 +88,61 @@ struct TablesT {
 };
 using Tables = TablesT<Shape16>;
 
+// The same Panda (Shape16) model constants packed per joint, for the lane-per-env code (pbre_fast.hpp).  `Tables` is lane-SoA -- right for
+// the 16-lane row kernels, where lane j loads T.x[j] -- but the lane-per-env code reads it as scalars with a compile-time joint index: the
+// 15 frame constants of one joint lie 64 bytes apart there, one s_load_dword each (or whole [k][0..15] rows that hold the values of joints
+// far ahead and stay live in SGPRs until they spill).  Here everything a joint's part of a sweep reads is one aligned record, in the order
+// the forward sweep reads it: one s_load_dwordx16 / x8 / x4 per record.  The collision spheres are sorted by (owner link, index) so that
+// link j's are the range [s_begin[j], s_begin[j + 1]) -- no scan over all spheres with an owner test per link.
+// Filled by pack_fast_tables() from a finished `Tables` (the single source of truth) wherever that is uploaded or refreshed.
+struct FastTables {
+    static constexpr int NJ = Shape16::NJ, NSUB = Shape16::NSUB, NS = Shape16::W;      // NS: sphere records (build_tables: <= 16 spheres)
+    struct alignas(64) Frame  { float axis[3], R0[9], p0[3], pad; };                   // joint frame w.r.t. the parent link at q = 0
+    struct alignas(64) Sub    { float m, c[3], I[6], pad[6]; };                        // rigid sub-body: mass, COM, inertia xx yy zz xy xz yz
+    struct alignas(64) Joint  { float lower, upper, home, rst_q, kp_hold, kd_hold, kp_act, kd_act, jdamp, pad[7]; };
+    struct alignas(32) Sphere { float c[3], r, mu; int idx, owner, pad; };             // idx: the sphere's index in `Tables` (candidate tie-break)
+    Frame  fr[NJ];
+    Sub    sb[NJ][NSUB];
+    Joint  jt[NJ];
+    Sphere sph[NS];
+    alignas(64) int s_begin[NJ + 1];
+    int    ndof, n_act, n_obs_j, nspheres, ee_owner, pad_[1];
+    alignas(64) float ee_R[9], ee_p[3], ee_lp[3], pad2_[1];
+};
+static_assert(sizeof(FastTables::Frame) == 64 && sizeof(FastTables::Sub) == 64 && sizeof(FastTables::Joint) == 64 && sizeof(FastTables::Sphere) == 32, "one scalar load per record");
+
+inline void pack_fast_tables(const Tables& T, FastTables& F) {
+    constexpr int NJ = FastTables::NJ, NSUB = FastTables::NSUB;
+    std::memset(&F, 0, sizeof F);
+    for (int j = 0; j < NJ; j++) {
+        for (int k = 0; k < 3; k++) { F.fr[j].axis[k] = T.axis[k][j]; F.fr[j].p0[k] = T.p0[k][j]; }
+        for (int k = 0; k < 9; k++) F.fr[j].R0[k] = T.R0[k][j];
+        for (int b = 0; b < NSUB; b++) {
+            F.sb[j][b].m = T.sb_m[b][j];
+            for (int k = 0; k < 3; k++) F.sb[j][b].c[k] = T.sb_c[b][k][j];
+            for (int k = 0; k < 6; k++) F.sb[j][b].I[k] = T.sb_I[b][k][j];
+        }
+        FastTables::Joint& r = F.jt[j];
+        r.lower = T.lower[j]; r.upper = T.upper[j]; r.home = T.home[j]; r.rst_q = T.rst_q[j]; r.jdamp = T.jdamp[j];
+        r.kp_hold = T.kp_hold[j]; r.kd_hold = T.kd_hold[j]; r.kp_act = T.kp_act[j]; r.kd_act = T.kd_act[j];
+    }
+    const int ns = T.nspheres < 0 ? 0 : (T.nspheres > FastTables::NS ? FastTables::NS : T.nspheres);
+    int n = 0;
+    for (int j = 0; j < NJ; j++) {           // stable: within a link the spheres keep their order
+        F.s_begin[j] = n;
+        for (int s = 0; s < ns; s++) {
+            if (T.s_owner[s] != j) continue;
+            FastTables::Sphere& r = F.sph[n++];
+            for (int k = 0; k < 3; k++) r.c[k] = T.s_c[k][s];
+            r.r = T.s_r[s]; r.mu = T.s_mu[s]; r.idx = s; r.owner = j;
+        }
+    }
+    F.s_begin[NJ] = n;
+    F.ndof = T.ndof; F.n_act = T.n_act; F.n_obs_j = T.n_obs_j; F.nspheres = n; F.ee_owner = T.ee_owner;
+    for (int k = 0; k < 9; k++) F.ee_R[k] = T.ee_R[k];
+    for (int k = 0; k < 3; k++) { F.ee_p[k] = T.ee_p[k]; F.ee_lp[k] = T.ee_lp[k]; }
+}
+
 struct Params {                  // float copies of pbre_physics + task constants used on device
     float dt, inv_dt, gz;
     int   iters;
