@@ -40,6 +40,9 @@ def test_contact_rich_states(panda, hip_lib, flags):
 
 @pytest.mark.parametrize("flags", [_capi.F_COMPLEX_ROWS, _capi.F_COMPLEX_LANES])
 def test_joint_limit_rows(panda, hip_lib, flags):
+    """Four envs with joints 3, 5, 7 and 1 past a limit.  Under both flags they share one wave, so that wave has four limit joints and
+    takes the loop with per-joint tests (k_row_list: `ro_sweeps<-1>`); the nine copies with ONE joint's limit row inlined, and every other
+    per-wave path of Core::step, are reached on purpose in tests/test_gpu_row_paths.py."""
     eng, ora = parity.make_pair(_capi.Engine, hip_lib, panda["table"], 4, flags=flags)
     st, _ = ora.batch_reset(4)
     st[0, 3] = 0.02
