@@ -7,6 +7,7 @@
 //   k_cam_rays   one 256-thread workgroup per (env, strip of 256 consecutive pixels): the env's records are copied to LDS once (<= 6208
 //                bytes), every thread casts one ray through all of them (a loop over the runtime count, not unrolled), then the object in
 //                its own frame, the table and the floor.  All three outputs are stored coalesced.  No atomics, nothing between workgroups.
+// The ctx's record (CamState), the link table and the forward kinematics are pbre_scene.hpp's, shared with the contact query.
 // Neither kernel writes the state.  The per-ray functions are in pbre_camera.hpp (shared with the host tests).
 #include <hip/hip_runtime.h>
 #include <algorithm>
@@ -17,26 +18,13 @@
 #include "../../include/pbre_camera.h"
 #include "pbre_engine.hpp"
 #include "pbre_tables.hpp"
+#include "pbre_scene.hpp"
 #define PBRE_HD __host__ __device__ __forceinline__
 #include "pbre_camera.hpp"
 
 namespace pbre {
 
-constexpr int CT_HDR = 16, CT_LINK = 20;        // device table: [0] n_links [1] n_prims [2..4] base position [5..13] base rotation; links; primitives
 constexpr int CAM_TPB = 256, SCENE_TPB = 64;
-
-struct CamState {
-    std::vector<double> table;                  // the RobotTable (include/pbre.h)
-    int nl = 0, ns = 0, ndof = 0;
-    std::vector<float> visuals;                 // the caller's list (12 floats each); empty: the collision spheres
-    int nprims = 0;
-    bool dirty = true;                          // the device table is older than the list
-    int device = -1;
-    float *d_table = nullptr, *d_frames = nullptr, *d_scene = nullptr, *d_views = nullptr;
-    int cap_n = 0, cap_prims = -1;
-    size_t cap_table = 0;
-    void* d_img = nullptr; size_t cap_img = 0;  // images of the host-buffer render
-};
 
 struct RayParams {
     const float* scene; int sstride, nprims;
@@ -59,40 +47,7 @@ __global__ __launch_bounds__(SCENE_TPB) void k_cam_scene(const float* __restrict
     const float* st = state + (size_t)env * stride;
     const int nl = (int)tab[0], np = (int)tab[1];
     const size_t N = (size_t)n;
-#pragma unroll 1
-    for (int i = 0; i < nl; i++) {
-        const float* L = tab + CT_HDR + CT_LINK * i;
-        const int par = (int)L[0], jt = (int)L[1], dof = (int)L[17];
-        float Rp[9], pp[3];
-        if (par >= 0) {
-            const float* F = frames + (size_t)par * 12 * N + env;
-            for (int k = 0; k < 9; k++) Rp[k] = F[k * N];
-            for (int k = 0; k < 3; k++) pp[k] = F[(9 + k) * N];
-        } else {
-            for (int k = 0; k < 9; k++) Rp[k] = tab[5 + k];
-            for (int k = 0; k < 3; k++) pp[k] = tab[2 + k];
-        }
-        float Rl[9], pl[3] = {L[5], L[6], L[7]};
-        for (int k = 0; k < 9; k++) Rl[k] = L[8 + k];
-        if (jt == 1) {                       // revolute: R0 (I + s K + (1 - c) K^2)
-            const float q = st[dof], s = sinf(q), c1 = 1.0f - cosf(q);
-            const float ax = L[2], ay = L[3], az = L[4];
-            const float A[9] = {1.0f - c1 * (ay * ay + az * az), -s * az + c1 * ax * ay, s * ay + c1 * ax * az,
-                                s * az + c1 * ax * ay, 1.0f - c1 * (ax * ax + az * az), -s * ax + c1 * ay * az,
-                                -s * ay + c1 * ax * az, s * ax + c1 * ay * az, 1.0f - c1 * (ax * ax + ay * ay)};
-            float M[9];
-            for (int r = 0; r < 3; r++) for (int c = 0; c < 3; c++) M[3 * r + c] = Rl[3 * r] * A[c] + Rl[3 * r + 1] * A[3 + c] + Rl[3 * r + 2] * A[6 + c];
-            for (int k = 0; k < 9; k++) Rl[k] = M[k];
-        } else if (jt == 2) {                // prismatic: xyz + (R0 axis) q
-            const float q = st[dof];
-            for (int r = 0; r < 3; r++) pl[r] += (Rl[3 * r] * L[2] + Rl[3 * r + 1] * L[3] + Rl[3 * r + 2] * L[4]) * q;
-        }
-        float* F = frames + (size_t)i * 12 * N + env;
-        for (int r = 0; r < 3; r++) {
-            for (int c = 0; c < 3; c++) F[(3 * r + c) * N] = Rp[3 * r] * Rl[c] + Rp[3 * r + 1] * Rl[3 + c] + Rp[3 * r + 2] * Rl[6 + c];
-            F[(9 + r) * N] = pp[r] + Rp[3 * r] * pl[0] + Rp[3 * r + 1] * pl[1] + Rp[3 * r + 2] * pl[2];
-        }
-    }
+    scene_fk(tab, st, env, N, frames);
     float* sc = scene + (size_t)env * sstride;
 #pragma unroll 1
     for (int k = 0; k < np; k++) {
@@ -245,7 +200,7 @@ extern "C" __attribute__((visibility("hidden"))) void pbre_camera_state_free(Cam
     if (!s) return;
     if (s->device >= 0) {
         (void)hipSetDevice(s->device);
-        for (void* p : {(void*)s->d_table, (void*)s->d_frames, (void*)s->d_scene, (void*)s->d_views, s->d_img}) if (p) (void)hipFree(p);
+        for (void* p : {(void*)s->d_table, (void*)s->d_frames, (void*)s->d_scene, (void*)s->d_views, s->d_img, (void*)s->d_cq_table, (void*)s->d_cq_frames, s->d_cq_out}) if (p) (void)hipFree(p);
     }
     delete s;
 }
@@ -259,18 +214,7 @@ static unsigned pack_colour(int link, const float* rgb) {
 // the float table of the device (see CT_HDR): links of the RobotTable, then the primitives
 static std::vector<float> build_device_table(const CamState& s, int& nprims) {
     const double* t = s.table.data();
-    std::vector<float> out(CT_HDR + (size_t)CT_LINK * s.nl, 0.0f);
-    out[0] = (float)s.nl;
-    for (int k = 0; k < 3; k++) out[2 + k] = (float)t[6 + k];
-    for (int k = 0; k < 9; k++) out[5 + k] = (float)t[9 + k];
-    for (int i = 0; i < s.nl; i++) {
-        const double* r = t + 24 + i * 40;
-        float* L = out.data() + CT_HDR + CT_LINK * i;
-        L[0] = (float)r[0]; L[1] = (float)r[1];
-        for (int k = 0; k < 3; k++) { L[2 + k] = (float)r[2 + k]; L[5 + k] = (float)r[5 + k]; }
-        for (int k = 0; k < 9; k++) L[8 + k] = (float)r[8 + k];
-        L[17] = (float)r[33];
-    }
+    std::vector<float> out = scene_link_table(s);
     auto put = [&](int link, const float* a, const float* b, float rad, const float* rgb) {
         float rec[PBRE_CAM_PRIM_FLOATS] = {(float)link, a[0], a[1], a[2], b[0], b[1], b[2], rad, 0, 0, 0, 0};
         const unsigned w = pack_colour(link, rgb);

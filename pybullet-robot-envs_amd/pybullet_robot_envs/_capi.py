@@ -59,6 +59,13 @@ class Camera(C.Structure):
                 ("background", C.c_float * 3), ("floor_rgb", C.c_float * 3), ("table_rgb", C.c_float * 3), ("object_rgb", C.c_float * 3)]
 
 
+class ContactOut(C.Structure):
+    """pbre_contact_out (include/pbre_contacts.h)"""
+    _fields_ = [("flags", C.c_void_p), ("dist", C.c_void_p), ("nearest", C.c_void_p), ("count", C.c_void_p), ("tips", C.c_void_p)]
+
+
+CQ_FAR = 3.0e38        # PBRE_CQ_FAR: "no such pair" in contact_query()["dist"]
+
 _LIB = None
 
 
@@ -101,6 +108,11 @@ def load(path=None):
         lib.pbre_camera_set_visuals.argtypes = [C.c_void_p, C.c_void_p, C.c_int32]
         lib.pbre_camera_render_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         lib.pbre_camera_render.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    if hasattr(lib, "pbre_contact_query"):       # the contact query (include/pbre_contacts.h); the host emulation library has none
+        for name in ("pbre_contact_query_device", "pbre_contact_query"):
+            getattr(lib, name).restype = C.c_int
+        lib.pbre_contact_query_device.argtypes = [C.c_void_p, C.c_void_p, C.c_float, C.c_void_p]
+        lib.pbre_contact_query.argtypes = [C.c_void_p, C.c_void_p, C.c_float]
     if path is None:
         _LIB = lib
     return lib
@@ -578,6 +590,41 @@ class Engine:
         self._chk(self.lib.pbre_camera_render(self._ctx, C.byref(cam), ptr("depth"), ptr("seg"), ptr("rgba")))
         return res
 
+    # ---- the contact query (include/pbre_contacts.h; csrc/pbre_contacts.hip) ----
+    def contact_query(self, margin=None, out="numpy", flags=True, dist=True, nearest=True, count=True, tips=True):
+        """Per env, from the state on the device: "flags" int32 [N] (model/contacts.py: OBJECT_TABLE | ROBOT_OBJECT | ROBOT_TABLE), "dist"
+        float32 [N, 3] (smallest signed distance object-table, robot-object, robot-table; CQ_FAR: no such pair), "nearest" int32 [N, 2]
+        (the collision sphere attaining dist[1] / dist[2], -1: none; model/table.py: sphere_links names its link), "count" int32 [N, 2]
+        (spheres within the margin of the object / the table) and "tips" int32 [N] (bit s: fingertip slot s touches the object), each only
+        when asked for.  margin None: the engine's contact margin; a value >= 0 overrides it for this call.  out="numpy": host arrays,
+        synchronous.  out="torch": tensors on the engine's device, enqueued on torch's current stream behind whatever step was enqueued
+        there (asynchronous)."""
+        if not hasattr(self.lib, "pbre_contact_query"):
+            raise RuntimeError("contact_query: this library has no contact query (no pbre_contact_query symbol; the host emulation "
+                               "library answers WorldEnv.check_contact on the host instead)")
+        n = self.num_envs
+        want = [("flags", flags, (n,), "int32"), ("dist", dist, (n, 3), "float32"), ("nearest", nearest, (n, 2), "int32"),
+                ("count", count, (n, 2), "int32"), ("tips", tips, (n,), "int32")]
+        mg = C.c_float(-1.0 if margin is None else float(margin))
+        res, o = {}, ContactOut()
+        if out == "torch":
+            import torch
+            dev = torch.device("cuda", int(self.cfg.device_id))
+            for k, on, shape, dt in want:
+                if on:
+                    res[k] = torch.empty(shape, dtype=getattr(torch, dt), device=dev)
+                    setattr(o, k, res[k].data_ptr())
+            self._chk(self.lib.pbre_contact_query_device(self._ctx, C.byref(o), mg, C.c_void_p(torch_stream(dev))))
+            return res
+        if out != "numpy":
+            raise ValueError("contact_query: out must be 'numpy' or 'torch'")
+        for k, on, shape, dt in want:
+            if on:
+                res[k] = np.empty(shape, dt)
+                setattr(o, k, res[k].ctypes.data)
+        self._chk(self.lib.pbre_contact_query(self._ctx, C.byref(o), mg))
+        return res
+
 
 class MultiEngine(object):
     """`num_envs` environments sharded over several GPUs of one node from ONE process (the Gym classes' `devices=[...]` kwarg, SURVEY
@@ -622,6 +669,12 @@ class MultiEngine(object):
 
     def render(self, *a, **kw):
         raise NotImplementedError("render: one device per engine")
+
+    def contact_query(self, margin=None, out="numpy", **kw):
+        if out != "numpy":
+            raise NotImplementedError("contact_query(out='torch'): one device per engine (use shards[k].contact_query)")
+        parts = self._map(lambda k: self.shards[k].contact_query(margin, **kw))
+        return {key: self._cat([p[key] for p in parts]) for key in parts[0]}
 
     def reset(self, mask=None):
         m = None if mask is None else np.ascontiguousarray(mask, dtype=np.uint8)

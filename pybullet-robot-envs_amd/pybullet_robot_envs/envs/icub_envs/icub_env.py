@@ -207,6 +207,12 @@ class iCubEnv:
                                "to iCubEnv used alone (see the module docstring)")
         return eng
 
+    def contact_info(self, margin=None):
+        """Contact flags, smallest distances, nearest collision spheres, counts and the fingertip mask of every env, from the batched
+        contact query on the device (include/pbre_contacts.h; Engine.contact_query): a dict of numpy arrays.  Read-only, so it also
+        answers inside a task env.  margin: None = the engine's contact margin, else a distance in metres."""
+        return self._engine_or_build().contact_query(margin)
+
     @property
     def num_envs(self):
         return self._client.num_envs

@@ -211,6 +211,18 @@ class PandaTaskBase(Env):
         step_tensor on that stream they show the state it produced)."""
         return self._engine.render(self._camera(width, height), depth=depth, seg=seg, rgb=rgb, out="torch")
 
+    def contact_info(self, margin=None):
+        """Contact flags and proximities of every env from the batched contact query (include/pbre_contacts.h), as numpy arrays:
+        "flags" int32 [N] (model/contacts.py: OBJECT_TABLE | ROBOT_OBJECT | ROBOT_TABLE), "dist" float32 [N, 3] (object-table,
+        robot-object, robot-table), "nearest" int32 [N, 2] (collision-sphere index; model/table.py: sphere_links), "count" int32 [N, 2],
+        "tips" int32 [N].  margin: None = the engine's contact margin, else a distance in metres ("within 1 cm": 0.01)."""
+        return self._engine.contact_query(margin)
+
+    def contact_tensor(self, margin=None):
+        """The same without a host hop: tensors on the engine's device, computed on torch's current stream (so after a step_tensor on
+        that stream they describe the state it produced) -- contact rewards, safety termination, grasp detection."""
+        return self._engine.contact_query(margin, out="torch")
+
     # ------------------------------------------------------------------ reference attributes
     @property
     def _env_step_counter(self):

@@ -274,6 +274,12 @@ class pandaEnv:
         c = (t[:, 6] - t[:, 5]) > 0
         return bool(c[0]) if self.num_envs == 1 else c
 
+    def contact_info(self, margin=None):
+        """Contact flags, smallest distances, nearest collision spheres, counts and the fingertip mask of every env, from the batched
+        contact query on the device (include/pbre_contacts.h; Engine.contact_query): a dict of numpy arrays.  Read-only, so it also
+        answers inside a task env.  margin: None = the engine's contact margin, else a distance in metres."""
+        return self._engine_or_build().contact_query(margin)
+
     def get_object_pose(self):
         """[N, 7] position + quaternion of the object of the demo scene (the demo reads it back through PyBullet)."""
         eng = self._engine_or_build()
