@@ -200,7 +200,8 @@ extern "C" __attribute__((visibility("hidden"))) void pbre_camera_state_free(Cam
     if (!s) return;
     if (s->device >= 0) {
         (void)hipSetDevice(s->device);
-        for (void* p : {(void*)s->d_table, (void*)s->d_frames, (void*)s->d_scene, (void*)s->d_views, s->d_img, (void*)s->d_cq_table, (void*)s->d_cq_frames, s->d_cq_out}) if (p) (void)hipFree(p);
+        for (void* p : {(void*)s->d_table, (void*)s->d_frames, (void*)s->d_scene, (void*)s->d_views, s->d_img, (void*)s->d_cq_table, (void*)s->d_cq_frames, s->d_cq_out,
+                        (void*)s->d_kin_table, (void*)s->d_kin_cols, s->d_kin_out}) if (p) (void)hipFree(p);
     }
     delete s;
 }

@@ -26,6 +26,11 @@ struct CamState {
     float *d_cq_table = nullptr, *d_cq_frames = nullptr;
     void* d_cq_out = nullptr;
     int cq_cap_n = 0, cq_cap_out = 0;
+    // the kinematics query's (pbre_kin.hip), its own so that a contact query on another stream cannot race with it: the link table with
+    // masses and inertias (uploaded once), the column buffers of one query, and the outputs of the host-buffer query
+    float *d_kin_table = nullptr, *d_kin_cols = nullptr;
+    void* d_kin_out = nullptr;
+    size_t kin_cap_cols = 0, kin_cap_out = 0;
 };
 
 // header and links of the device table (see CT_HDR), from the RobotTable

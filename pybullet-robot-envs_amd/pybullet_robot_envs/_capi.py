@@ -66,6 +66,13 @@ class ContactOut(C.Structure):
 
 CQ_FAR = 3.0e38        # PBRE_CQ_FAR: "no such pair" in contact_query()["dist"]
 
+
+class KinQuery(C.Structure):
+    """pbre_kin_query_t (include/pbre_kin.h)"""
+    _fields_ = [("links", C.c_void_p), ("n_links", C.c_int32), ("at_com", C.c_int32), ("jac_link", C.c_int32), ("jac_point", C.c_float * 3),
+                ("jac_at_com", C.c_int32), ("qdd", C.c_void_p),
+                ("pose", C.c_void_p), ("vel", C.c_void_p), ("jac", C.c_void_p), ("mass", C.c_void_p), ("tau", C.c_void_p)]
+
 _LIB = None
 
 
@@ -113,6 +120,11 @@ def load(path=None):
             getattr(lib, name).restype = C.c_int
         lib.pbre_contact_query_device.argtypes = [C.c_void_p, C.c_void_p, C.c_float, C.c_void_p]
         lib.pbre_contact_query.argtypes = [C.c_void_p, C.c_void_p, C.c_float]
+    if hasattr(lib, "pbre_kin_query"):           # the kinematics / dynamics query (include/pbre_kin.h); the host emulation library has none
+        for name in ("pbre_kin_query_device", "pbre_kin_query"):
+            getattr(lib, name).restype = C.c_int
+        lib.pbre_kin_query_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+        lib.pbre_kin_query.argtypes = [C.c_void_p, C.c_void_p]
     if path is None:
         _LIB = lib
     return lib
@@ -625,6 +637,62 @@ class Engine:
         self._chk(self.lib.pbre_contact_query(self._ctx, C.byref(o), mg))
         return res
 
+    # ---- the kinematics / dynamics query (include/pbre_kin.h; csrc/pbre_kin.hip) ----
+    def kin_query(self, links=None, at_com=False, jac_link=None, jac_point=(0, 0, 0), jac_at_com=False, qdd=None, out="numpy",
+                  pose=True, vel=True, jac=True, mass=True, tau=True):
+        """Per env, from the state on the device, each only when asked for (float32, world frame): "pose" [N, n_links, 7] (position,
+        quaternion x y z w with w >= 0) and "vel" [N, n_links, 6] (linear, angular) of the links `links` (indices into the RobotTable;
+        None: every link; at_com: the centre of mass instead of the link frame's origin, as p.getLinkState's [0] / [6]), "jac" [N, 6, nd] of
+        the point jac_point of link jac_link (None: the table's ee_link; jac_at_com: its centre of mass), "mass" [N, nd, nd] = M(q), and
+        "tau" [N, nd] = the inverse dynamics of (q, qd, qdd) under gravity (qdd None: zeros -- gravity plus Coriolis / centrifugal
+        torques).  Rigid bodies only: no joint or link damping, motors, limits or contacts.  out="numpy": host arrays, synchronous.
+        out="torch": tensors on the engine's device, enqueued on torch's current stream behind whatever step was enqueued there
+        (asynchronous); qdd may then be a CUDA tensor."""
+        if not hasattr(self.lib, "pbre_kin_query"):
+            raise RuntimeError("kin_query: this library has no kinematics query (no pbre_kin_query symbol; the host emulation library "
+                               "has none -- compute from get_state() on the host instead)")
+        if out not in ("numpy", "torch"):
+            raise ValueError("kin_query: out must be 'numpy' or 'torch'")
+        n, nd = self.num_envs, self.ndof
+        if links is None:
+            links = np.arange(int(self._table[2]), dtype=np.int32) if (pose or vel) else np.zeros(0, np.int32)
+        links = np.ascontiguousarray(np.asarray(links).reshape(-1), dtype=np.int32)
+        nlq = len(links)
+        want = [("pose", pose and nlq > 0, (n, nlq, 7)), ("vel", vel and nlq > 0, (n, nlq, 6)), ("jac", jac, (n, 6, nd)), ("mass", mass, (n, nd, nd)),
+                ("tau", tau, (n, nd))]
+        o = KinQuery()
+        o.links, o.n_links = (links.ctypes.data if nlq else None), nlq
+        o.at_com, o.jac_at_com = int(bool(at_com)), int(bool(jac_at_com))
+        o.jac_link = -1 if jac_link is None else int(jac_link)
+        for k in range(3):
+            o.jac_point[k] = float(jac_point[k])
+        res = {}
+        if out == "torch":
+            import torch
+            dev = torch.device("cuda", int(self.cfg.device_id))
+            if qdd is not None and tau:
+                qdd = torch.as_tensor(qdd, dtype=torch.float32, device=dev).contiguous()      # (a host array: uploaded on torch's current stream)
+                if tuple(qdd.shape) != (n, nd):
+                    raise ValueError("kin_query: qdd must have shape (%d, %d)" % (n, nd))
+                o.qdd = qdd.data_ptr()
+            for k, on, shape in want:
+                if on:
+                    res[k] = torch.empty(shape, dtype=torch.float32, device=dev)
+                    setattr(o, k, res[k].data_ptr())
+            self._chk(self.lib.pbre_kin_query_device(self._ctx, C.byref(o), C.c_void_p(torch_stream(dev))))
+            return res
+        if qdd is not None and tau:
+            qdd = np.ascontiguousarray(qdd, dtype=np.float32)
+            if qdd.shape != (n, nd):
+                raise ValueError("kin_query: qdd must have shape (%d, %d)" % (n, nd))
+            o.qdd = qdd.ctypes.data
+        for k, on, shape in want:
+            if on:
+                res[k] = np.empty(shape, np.float32)
+                setattr(o, k, res[k].ctypes.data)
+        self._chk(self.lib.pbre_kin_query(self._ctx, C.byref(o)))
+        return res
+
 
 class MultiEngine(object):
     """`num_envs` environments sharded over several GPUs of one node from ONE process (the Gym classes' `devices=[...]` kwarg, SURVEY
@@ -674,6 +742,13 @@ class MultiEngine(object):
         if out != "numpy":
             raise NotImplementedError("contact_query(out='torch'): one device per engine (use shards[k].contact_query)")
         parts = self._map(lambda k: self.shards[k].contact_query(margin, **kw))
+        return {key: self._cat([p[key] for p in parts]) for key in parts[0]}
+
+    def kin_query(self, out="numpy", qdd=None, **kw):
+        if out != "numpy":
+            raise NotImplementedError("kin_query(out='torch'): one device per engine (use shards[k].kin_query)")
+        dd = None if qdd is None else np.ascontiguousarray(qdd, dtype=np.float32)
+        parts = self._map(lambda k: self.shards[k].kin_query(qdd=None if dd is None else dd[self._sl(k)], **kw))
         return {key: self._cat([p[key] for p in parts]) for key in parts[0]}
 
     def reset(self, mask=None):

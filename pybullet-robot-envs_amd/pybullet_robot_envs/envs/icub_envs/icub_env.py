@@ -213,6 +213,14 @@ class iCubEnv:
         answers inside a task env.  margin: None = the engine's contact margin, else a distance in metres."""
         return self._engine_or_build().contact_query(margin)
 
+    def kinematics_info(self, **kw):
+        """Link poses and velocities (p.getLinkState with computeLinkVelocity=1), the Jacobian of a point of a link (p.calculateJacobian),
+        M(q) (p.calculateMassMatrix) and the inverse-dynamics torques (p.calculateInverseDynamics) of every env, from the batched
+        kinematics query on the device (include/pbre_kin.h; the keyword arguments and the result of Engine.kin_query).  `links` and
+        `jac_link` also take the names of links of the simulated model.  Read-only, so it also answers inside a task env."""
+        from pybullet_robot_envs.model.table import kin_args
+        return self._engine_or_build().kin_query(**kin_args(self._sim_model, kw))
+
     @property
     def num_envs(self):
         return self._client.num_envs

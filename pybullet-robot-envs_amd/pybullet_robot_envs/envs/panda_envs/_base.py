@@ -223,6 +223,17 @@ class PandaTaskBase(Env):
         that stream they describe the state it produced) -- contact rewards, safety termination, grasp detection."""
         return self._engine.contact_query(margin, out="torch")
 
+    def kinematics_info(self, **kw):
+        """Link poses and velocities, the hand Jacobian, M(q) and the inverse-dynamics torques of every env from the batched kinematics
+        query (include/pbre_kin.h), as numpy arrays: the dict of `Engine.kin_query(**kw)` -- "pose" [N, n_links, 7], "vel" [N, n_links, 6],
+        "jac" [N, 6, nd], "mass" [N, nd, nd], "tau" [N, nd].  `links` and `jac_link` also take link names ("panda_link5", "l_hand")."""
+        return self._robot.kinematics_info(**kw)
+
+    def kinematics_tensor(self, **kw):
+        """The same without a host hop: tensors on the engine's device, computed on torch's current stream (so after a step_tensor on
+        that stream they describe the state it produced) -- operational-space control, link-pose rewards, torque costs."""
+        return self._robot.kinematics_info(out="torch", **kw)
+
     # ------------------------------------------------------------------ reference attributes
     @property
     def _env_step_counter(self):

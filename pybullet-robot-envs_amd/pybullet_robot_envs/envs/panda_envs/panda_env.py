@@ -280,6 +280,14 @@ class pandaEnv:
         answers inside a task env.  margin: None = the engine's contact margin, else a distance in metres."""
         return self._engine_or_build().contact_query(margin)
 
+    def kinematics_info(self, **kw):
+        """Link poses and velocities (p.getLinkState with computeLinkVelocity=1), the Jacobian of a point of a link (p.calculateJacobian),
+        M(q) (p.calculateMassMatrix) and the inverse-dynamics torques (p.calculateInverseDynamics) of every env, from the batched
+        kinematics query on the device (include/pbre_kin.h; the keyword arguments and the result of Engine.kin_query).  `links` and
+        `jac_link` also take the names of links of the simulated model.  Read-only, so it also answers inside a task env."""
+        from pybullet_robot_envs.model.table import kin_args
+        return self._engine_or_build().kin_query(**kin_args(self._model, kw))
+
     def get_object_pose(self):
         """[N, 7] position + quaternion of the object of the demo scene (the demo reads it back through PyBullet)."""
         eng = self._engine_or_build()

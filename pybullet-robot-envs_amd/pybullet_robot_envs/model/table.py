@@ -94,6 +94,36 @@ def sphere_links(table, model=None):
     return links, names
 
 
+def link_index(model, name):
+    """Index, in the RobotTable built from `model`, of the link called `name` ("panda_link5", "l_hand"): what Engine.kin_query takes as
+    `links` / `jac_link`.  An int passes through.  (A RobotTable itself holds no names: pass the model it was built from.)"""
+    if isinstance(name, (int, np.integer)):
+        return int(name)
+    if not isinstance(model, dict) or "links" not in model:
+        raise TypeError("link_index: link names need the model the RobotTable was built from (a table holds no names)")
+    names = [l["name"] for l in model["links"]]
+    if name not in names:
+        raise KeyError("no link %r in the model (links: %s)" % (name, ", ".join(names)))
+    return names.index(name)
+
+
+def dof_names(model):
+    """Joint name of every DoF, in the column order of Engine.kin_query()'s "jac", "mass" and "tau" (the table's dof_index order)"""
+    return [l.get("joint_name", l["name"]) for l in model["links"] if l["jtype"] != 0]
+
+
+def kin_args(model, kw):
+    """kin_query keyword arguments with link names replaced by indices (`links`: a name, an index or a list of either; `jac_link`)"""
+    kw = dict(kw)
+    if kw.get("links") is not None:
+        ls = kw["links"]
+        ls = [ls] if isinstance(ls, (str, int, np.integer)) else list(ls)
+        kw["links"] = [link_index(model, x) for x in ls]
+    if kw.get("jac_link") is not None:
+        kw["jac_link"] = link_index(model, kw["jac_link"])
+    return kw
+
+
 def save_model_json(model, path):
     with open(path, "w") as f:
         json.dump(model, f, indent=1)
