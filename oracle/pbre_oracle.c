@@ -456,11 +456,13 @@ static real sphere_shape(int shape, const real* sc, real sr, const real* bc, con
     cl[0] = ux * rc; cl[1] = uy * rc; cl[2] = zc;
     real df[3] = {dl[0] - cl[0], dl[1] - cl[1], dl[2] - cl[2]};
     real len = norm3(df);
-    if (len >= (real)1e-9) {                            /* centre outside the solid */
+    /* inside by the centre's coordinates, not only by a closest point nearer than 1e-9: the float build leaves a residue of that size in
+     * dl - u rho for a centre well inside, and its normal would be the direction of that residue */
+    const real er = h[0] - rho, ez = h[2] - (real)fabs((double)dl[2]);
+    if (len >= (real)1e-9 && !(er >= 0 && ez >= 0)) {   /* centre outside the solid */
         for (int k = 0; k < 3; k++) nl[k] = df[k] / len;
         dist = len - sr;
     } else {                                            /* inside: leave through the nearer of the lateral surface and the caps */
-        const real er = h[0] - rho, ez = h[2] - (real)fabs((double)dl[2]);
         if (er <= ez) { nl[0] = ux; nl[1] = uy; nl[2] = 0; cl[0] = ux * h[0]; cl[1] = uy * h[0]; cl[2] = dl[2]; dist = -er - sr; }
         else { nl[0] = 0; nl[1] = 0; nl[2] = dl[2] >= 0 ? (real)1 : (real)-1; cl[0] = dl[0]; cl[1] = dl[1]; cl[2] = nl[2] * h[2]; dist = -ez - sr; }
     }

@@ -51,9 +51,8 @@ static PBRE_HD float sphere_aabb_dist(const float* sc, float sr, const float* bc
 }
 
 // ... against a round object (shape 1: sphere of radius h[0]; 2: cylinder about local z, radius h[0], half height h[2]): the distance of
-// Shapes::sphere_round.  One difference: a centre inside the cylinder is recognised by rho <= radius and |z| <= half height, not only by a
-// closest point closer than 1e-9 -- in fp32 (dl - u rho) leaves a residue of that size for a centre well inside, and the query reports
-// distances, where the step only needs "below the margin"
+// Shapes::sphere_round, with its rule for a centre inside the cylinder: rho <= radius and |z| <= half height, not only a closest point
+// closer than 1e-9 -- in fp32 (dl - u rho) leaves a residue of that size for a centre well inside
 static PBRE_HD float sphere_round_dist(int shape, const float* sc, float sr, const float* c, const float* R, const float* h) {
     if (shape == 1) {
         const float d[3] = {sc[0] - c[0], sc[1] - c[1], sc[2] - c[2]};

@@ -317,10 +317,11 @@ struct Core {
         V3 cl = v3(ux * rc, uy * rc, zc);
         V3 df = sub(dl, cl);
         F len = norm(df);
-        B inside = L::lt(len, L::c(1e-9f));
+        F er = h.x - rho, ez = h.z - L::abs(dl.z);
+        // (inside by the centre's coordinates as well: fp32 leaves a residue above 1e-9 in df for a centre well inside -- Shapes::sphere_round)
+        B inside = L::bor(L::lt(len, L::c(1e-9f)), L::band(L::ge(er, zero), L::ge(ez, zero)));
         F il = one / L::max(len, L::c(1e-30f));
         V3 n_out = scl(df, il);
-        F er = h.x - rho, ez = h.z - L::abs(dl.z);
         B lat = L::le(er, ez);                         // leave through the lateral surface rather than a cap
         F sz = L::sel(L::ge(dl.z, zero), one, zero - one);
         V3 n_in = v3(L::sel(lat, ux, zero), L::sel(lat, uy, zero), L::sel(lat, zero, sz));

@@ -77,9 +77,11 @@ struct Shapes {
         const float df[3] = {dl[0] - cl[0], dl[1] - cl[1], dl[2] - cl[2]};
         const float len = sqrtf(fmaf(df[0], df[0], fmaf(df[1], df[1], df[2] * df[2])));
         float nl[3], dist;
-        if (len >= 1e-9f) { const float il = 1.f / len; nl[0] = df[0] * il; nl[1] = df[1] * il; nl[2] = df[2] * il; dist = len - sr; }
+        // A centre inside the solid is recognised by its coordinates, not only by a closest point nearer than 1e-9: in fp32 dl - u rho leaves a
+        // residue of that size once rho exceeds 2^-6 m, and the normal of a centre well inside would be the direction of that residue.
+        const float er = h[0] - rho, ez = h[2] - fabsf(dl[2]);
+        if (len >= 1e-9f && !(er >= 0.f && ez >= 0.f)) { const float il = 1.f / len; nl[0] = df[0] * il; nl[1] = df[1] * il; nl[2] = df[2] * il; dist = len - sr; }
         else {
-            const float er = h[0] - rho, ez = h[2] - fabsf(dl[2]);
             if (er <= ez) { nl[0] = ux; nl[1] = uy; nl[2] = 0.f; cl[0] = ux * h[0]; cl[1] = uy * h[0]; cl[2] = dl[2]; dist = -er - sr; }
             else { nl[0] = 0.f; nl[1] = 0.f; nl[2] = dl[2] >= 0.f ? 1.f : -1.f; cl[0] = dl[0]; cl[1] = dl[1]; cl[2] = nl[2] * h[2]; dist = -ez - sr; }
         }
