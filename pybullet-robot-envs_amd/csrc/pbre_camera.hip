@@ -7,7 +7,8 @@
 //   k_cam_rays   one 256-thread workgroup per (env, strip of 256 consecutive pixels): the env's records are copied to LDS once (<= 6208
 //                bytes), every thread casts one ray through all of them (a loop over the runtime count, not unrolled), then the object in
 //                its own frame, the table and the floor.  All three outputs are stored coalesced.  No atomics, nothing between workgroups.
-// The ctx's record (CamState), the link table and the forward kinematics are pbre_scene.hpp's, shared with the contact query.
+// The ctx's record (pbre_ctx::readers: the RobotTable copy, CamBufs), the link table and the forward kinematics are pbre_scene.hpp's, shared
+// with the contact query; the ctx is reached through pbre_engine.hpp (state_view, fail: pbre_capi.hip).
 // Neither kernel writes the state.  The per-ray functions are in pbre_camera.hpp (shared with the host tests).
 #include <hip/hip_runtime.h>
 #include <algorithm>
@@ -184,28 +185,6 @@ __global__ __launch_bounds__(CAM_TPB) void k_cam_rays(const RayParams P) {
 
 using namespace pbre;
 
-// pbre_capi.hip
-extern "C" __attribute__((visibility("hidden"))) int pbre_camera_view(pbre_ctx* c, CamView* v, void* stream, int host_sync, CamState** cam);
-extern "C" __attribute__((visibility("hidden"))) void pbre_camera_set_error(pbre_ctx* c, const char* msg);
-
-extern "C" __attribute__((visibility("hidden"))) CamState* pbre_camera_state_new(const double* t, size_t len) {
-    CamState* s = new CamState();
-    if (t && len >= 24 && t[0] == 1346523717.0) {
-        const int nl = (int)t[2], ns = (int)t[5];
-        if (nl >= 0 && ns >= 0 && len >= (size_t)(24 + nl * 40 + ns * 8)) { s->table.assign(t, t + 24 + nl * 40 + ns * 8); s->nl = nl; s->ns = ns; s->ndof = (int)t[3]; }
-    }
-    return s;
-}
-extern "C" __attribute__((visibility("hidden"))) void pbre_camera_state_free(CamState* s) {
-    if (!s) return;
-    if (s->device >= 0) {
-        (void)hipSetDevice(s->device);
-        for (void* p : {(void*)s->d_table, (void*)s->d_frames, (void*)s->d_scene, (void*)s->d_views, s->d_img, (void*)s->d_cq_table, (void*)s->d_cq_frames, s->d_cq_out,
-                        (void*)s->d_kin_table, (void*)s->d_kin_cols, s->d_kin_out}) if (p) (void)hipFree(p);
-    }
-    delete s;
-}
-
 static unsigned pack_colour(int link, const float* rgb) {
     unsigned w = (unsigned)link & 255u;
     for (int k = 0; k < 3; k++) w |= (unsigned)std::fmin(std::fmax(std::floor(255.0 * rgb[k] + 0.5), 0.0), 255.0) << (8 * (k + 1));
@@ -213,7 +192,7 @@ static unsigned pack_colour(int link, const float* rgb) {
 }
 
 // the float table of the device (see CT_HDR): links of the RobotTable, then the primitives
-static std::vector<float> build_device_table(const CamState& s, int& nprims) {
+static std::vector<float> build_device_table(const Readers& s, int& nprims) {
     const double* t = s.table.data();
     std::vector<float> out = scene_link_table(s);
     auto put = [&](int link, const float* a, const float* b, float rad, const float* rgb) {
@@ -223,9 +202,9 @@ static std::vector<float> build_device_table(const CamState& s, int& nprims) {
         out.insert(out.end(), rec, rec + PBRE_CAM_PRIM_FLOATS);
     };
     nprims = 0;
-    if (!s.visuals.empty()) {
-        for (size_t k = 0; k * PBRE_CAM_PRIM_FLOATS < s.visuals.size(); k++) {
-            const float* v = s.visuals.data() + k * PBRE_CAM_PRIM_FLOATS;
+    if (!s.cam.visuals.empty()) {
+        for (size_t k = 0; k * PBRE_CAM_PRIM_FLOATS < s.cam.visuals.size(); k++) {
+            const float* v = s.cam.visuals.data() + k * PBRE_CAM_PRIM_FLOATS;
             put((int)v[0], v + 1, v + 4, v[7], v + 8); nprims++;
         }
     } else {
@@ -240,8 +219,6 @@ static std::vector<float> build_device_table(const CamState& s, int& nprims) {
     return out;
 }
 
-static int fail(pbre_ctx* ctx, int code, const char* msg) { pbre_camera_set_error(ctx, msg); return code; }
-
 static int check_camera(pbre_ctx* ctx, const pbre_camera* cam) {
     if (!ctx) return fail(nullptr, PBRE_E_ARG, "pbre_camera_render: null ctx");
     if (!cam) return fail(ctx, PBRE_E_ARG, "pbre_camera_render: null camera");
@@ -254,42 +231,32 @@ static int check_camera(pbre_ctx* ctx, const pbre_camera* cam) {
 }
 
 // enqueue both kernels on v.stream; the outputs are device pointers (null: skipped)
-static int render_on(pbre_ctx* ctx, CamState* s, const CamView& v, const pbre_camera* cam, float* d_depth, int32_t* d_seg, uint8_t* d_rgba) {
-    if (s->table.empty()) return fail(ctx, PBRE_E_TABLE, "pbre_camera_render: the ctx has no RobotTable");
+static int render_on(pbre_ctx* ctx, const StateView& v, const pbre_camera* cam, float* d_depth, int32_t* d_seg, uint8_t* d_rgba) {
+    Readers& r = ctx->readers;
+    CamBufs& s = r.cam;
+    if (r.table.empty()) return fail(ctx, PBRE_E_TABLE, "pbre_camera_render: the ctx has no RobotTable");
     if ((long long)v.n * cam->width * cam->height > 2147483647LL) return fail(ctx, PBRE_E_ARG, "pbre_camera_render: num_envs x height x width exceeds INT32_MAX");
     hipStream_t st = (hipStream_t)v.stream;
-    s->device = v.device;
-    if (s->dirty) {
+    if (s.dirty) {
         int np = 0;
-        const std::vector<float> tab = build_device_table(*s, np);
+        const std::vector<float> tab = build_device_table(r, np);
         PBRE_CHK_ON(ctx, hipDeviceSynchronize());          // (rare: a render on another stream may still read the old table)
-        if (tab.size() > s->cap_table) {
-            if (s->d_table) PBRE_CHK_ON(ctx, hipFree(s->d_table));
-            s->d_table = nullptr; s->cap_table = 0;
-            PBRE_CHK_ON(ctx, hipMalloc(&s->d_table, tab.size() * sizeof(float)));
-            s->cap_table = tab.size();
-        }
-        PBRE_CHK_ON(ctx, hipMemcpy(s->d_table, tab.data(), tab.size() * sizeof(float), hipMemcpyHostToDevice));
-        s->nprims = np; s->dirty = false;
+        PBRE_CHK_ON(ctx, grow(s.table, s.cap_table, tab.size(), false));
+        PBRE_CHK_ON(ctx, hipMemcpy(s.table, tab.data(), tab.size() * sizeof(float), hipMemcpyHostToDevice));
+        s.nprims = np; s.dirty = false;
     }
-    const int sstride = 8 * s->nprims + 16;
-    if (v.n > s->cap_n || s->nprims > s->cap_prims) {
-        PBRE_CHK_ON(ctx, hipDeviceSynchronize());
-        for (float** p : {&s->d_frames, &s->d_scene, &s->d_views}) { if (*p) PBRE_CHK_ON(ctx, hipFree(*p)); *p = nullptr; }
-        s->cap_n = 0; s->cap_prims = -1;
-        PBRE_CHK_ON(ctx, hipMalloc(&s->d_frames, (size_t)std::max(s->nl, 1) * 12 * v.n * sizeof(float)));
-        PBRE_CHK_ON(ctx, hipMalloc(&s->d_scene, (size_t)v.n * sstride * sizeof(float)));
-        PBRE_CHK_ON(ctx, hipMalloc(&s->d_views, (size_t)v.n * 16 * sizeof(float)));
-        s->cap_n = v.n; s->cap_prims = s->nprims;
-    }
+    const int sstride = 8 * s.nprims + 16;
+    const size_t f_frames = (size_t)std::max(r.nl, 1) * 12 * v.n, f_scene = (size_t)v.n * sstride, f_views = (size_t)v.n * 16;
+    PBRE_CHK_ON(ctx, grow(s.work, s.cap_work, f_frames + f_scene + f_views, true));      // (more primitives: a longer scene)
+    float *d_frames = s.work, *d_scene = d_frames + f_frames, *d_views = d_scene + f_scene;
     if (cam->per_env_view) {                     // (the caller's array may be gone when this call returns: wait for its upload)
-        PBRE_CHK_ON(ctx, hipMemcpyAsync(s->d_views, cam->views, (size_t)v.n * 16 * sizeof(float), hipMemcpyHostToDevice, st));
+        PBRE_CHK_ON(ctx, hipMemcpyAsync(d_views, cam->views, f_views * sizeof(float), hipMemcpyHostToDevice, st));
         PBRE_CHK_ON(ctx, hipStreamSynchronize(st));
     }
     RayParams P;
     std::memset(&P, 0, sizeof P);
-    P.scene = s->d_scene; P.sstride = sstride; P.nprims = s->nprims;
-    P.views = cam->per_env_view ? s->d_views : nullptr;
+    P.scene = d_scene; P.sstride = sstride; P.nprims = s.nprims;
+    P.views = cam->per_env_view ? d_views : nullptr;
     for (int k = 0; k < 16; k++) P.view[k] = cam->view[k];
     P.tx = 1.0f / cam->proj[0]; P.ty = 1.0f / cam->proj[5]; P.cx = cam->proj[8]; P.cy = cam->proj[9];
     P.znear = cam->proj[14] / (cam->proj[10] - 1.0f); P.zfar = cam->proj[14] / (cam->proj[10] + 1.0f);
@@ -305,7 +272,7 @@ static int render_on(pbre_ctx* ctx, CamState* s, const CamView& v, const pbre_ca
     P.hull = v.hull;
     if (P.obj_shape == PBRE_SHAPE_HULL && !P.hull) return fail(ctx, PBRE_E_ARG, "pbre_camera_render: a hull object without a hull table");
     P.depth = d_depth; P.seg = d_seg; P.rgba = (uchar4*)d_rgba;
-    hipLaunchKernelGGL(k_cam_scene, dim3((v.n + SCENE_TPB - 1) / SCENE_TPB), dim3(SCENE_TPB), 0, st, s->d_table, v.state, v.stride, v.n, v.obj_lane, s->d_frames, s->d_scene, sstride);
+    hipLaunchKernelGGL(k_cam_scene, dim3((v.n + SCENE_TPB - 1) / SCENE_TPB), dim3(SCENE_TPB), 0, st, (const float*)s.table, v.state, v.stride, v.n, v.obj_lane, d_frames, d_scene, sstride);
     PBRE_CHK_ON(ctx, hipGetLastError());
     if (d_depth || d_seg || d_rgba) {
         hipLaunchKernelGGL(k_cam_rays, dim3((unsigned)v.n * (unsigned)P.strips), dim3(CAM_TPB), 0, st, P);
@@ -349,53 +316,43 @@ int pbre_camera_default(pbre_camera* cam, int32_t width, int32_t height) {
 
 int pbre_camera_set_visuals(pbre_ctx* ctx, const float* records, int32_t n) {
     if (!ctx) return fail(nullptr, PBRE_E_ARG, "pbre_camera_set_visuals: null ctx");
-    CamView v; CamState* s = nullptr;
-    const int rc = pbre_camera_view(ctx, &v, nullptr, 0, &s);
+    StateView v;
+    const int rc = ctx->state_view(&v, nullptr, false);
     if (rc != PBRE_OK) return rc;
-    if (!s || n < 0 || (n > 0 && !records)) return fail(ctx, PBRE_E_ARG, "pbre_camera_set_visuals: bad arguments");
+    if (n < 0 || (n > 0 && !records)) return fail(ctx, PBRE_E_ARG, "pbre_camera_set_visuals: bad arguments");
     if (n > PBRE_CAM_MAX_PRIMS) return fail(ctx, PBRE_E_ARG, "pbre_camera_set_visuals: more than 192 primitives");
     for (int k = 0; k < n; k++) {
         const float* r = records + (size_t)k * PBRE_CAM_PRIM_FLOATS;
-        bool ok = r[0] >= 0.0f && r[0] < (float)s->nl && r[0] < 256.0f && r[0] == std::floor(r[0]) && r[7] >= 0.0f;
+        bool ok = r[0] >= 0.0f && r[0] < (float)ctx->readers.nl && r[0] < 256.0f && r[0] == std::floor(r[0]) && r[7] >= 0.0f;
         for (int j = 1; j < 11; j++) ok = ok && std::isfinite(r[j]);
         if (!ok) return fail(ctx, PBRE_E_ARG, "pbre_camera_set_visuals: bad record (link index out of range, negative radius or a non-finite value)");
     }
-    s->visuals.assign(records, records + (size_t)n * PBRE_CAM_PRIM_FLOATS);
-    s->dirty = true;
+    ctx->readers.cam.visuals.assign(records, records + (size_t)n * PBRE_CAM_PRIM_FLOATS);
+    ctx->readers.cam.dirty = true;
     return PBRE_OK;
 }
 
 int pbre_camera_render_device(pbre_ctx* ctx, const pbre_camera* cam, float* d_depth, int32_t* d_seg, uint8_t* d_rgba, void* stream) {
     int rc = check_camera(ctx, cam);
     if (rc != PBRE_OK) return rc;
-    CamView v; CamState* s = nullptr;
-    if ((rc = pbre_camera_view(ctx, &v, stream, 0, &s)) != PBRE_OK) return rc;
-    return render_on(ctx, s, v, cam, d_depth, d_seg, d_rgba);
+    StateView v;
+    if ((rc = ctx->state_view(&v, stream, false)) != PBRE_OK) return rc;
+    return render_on(ctx, v, cam, d_depth, d_seg, d_rgba);
 }
 
 int pbre_camera_render(pbre_ctx* ctx, const pbre_camera* cam, float* depth, int32_t* seg, uint8_t* rgba) {
     int rc = check_camera(ctx, cam);
     if (rc != PBRE_OK) return rc;
-    CamView v; CamState* s = nullptr;
-    if ((rc = pbre_camera_view(ctx, &v, nullptr, 1, &s)) != PBRE_OK) return rc;
+    StateView v;
+    if ((rc = ctx->state_view(&v, nullptr, true)) != PBRE_OK) return rc;
     if ((long long)v.n * cam->width * cam->height > 2147483647LL) return fail(ctx, PBRE_E_ARG, "pbre_camera_render: num_envs x height x width exceeds INT32_MAX");
     const size_t px = (size_t)v.n * cam->width * cam->height;
-    const size_t need = px * 12;                 // depth | seg | rgba, 4 bytes per pixel each
-    if (need > s->cap_img) {
-        if (s->d_img) PBRE_CHK_ON(ctx, hipFree(s->d_img));
-        s->d_img = nullptr; s->cap_img = 0;
-        PBRE_CHK_ON(ctx, hipMalloc(&s->d_img, need));
-        s->cap_img = need;
-    }
-    float* dd = depth ? (float*)s->d_img : nullptr;
-    int32_t* ds = seg ? (int32_t*)((char*)s->d_img + px * 4) : nullptr;
-    uint8_t* dc = rgba ? (uint8_t*)s->d_img + px * 8 : nullptr;
-    if ((rc = render_on(ctx, s, v, cam, dd, ds, dc)) != PBRE_OK) return rc;
     hipStream_t st = (hipStream_t)v.stream;
-    if (depth) PBRE_CHK_ON(ctx, hipMemcpyAsync(depth, dd, px * 4, hipMemcpyDeviceToHost, st));
-    if (seg) PBRE_CHK_ON(ctx, hipMemcpyAsync(seg, ds, px * 4, hipMemcpyDeviceToHost, st));
-    if (rgba) PBRE_CHK_ON(ctx, hipMemcpyAsync(rgba, dc, px * 4, hipMemcpyDeviceToHost, st));
-    PBRE_CHK_ON(ctx, hipStreamSynchronize(st));
+    Stage sg;                                    // depth | seg | rgba, 4 bytes per pixel each
+    const int i_depth = sg.add(depth, px * 4), i_seg = sg.add(seg, px * 4), i_rgba = sg.add(rgba, px * 4);
+    PBRE_CHK_ON(ctx, sg.begin(ctx->readers.cam.out, ctx->readers.cam.cap_out, st));
+    if ((rc = render_on(ctx, v, cam, sg.dev<float>(i_depth), sg.dev<int32_t>(i_seg), sg.dev<uint8_t>(i_rgba))) != PBRE_OK) return rc;
+    PBRE_CHK_ON(ctx, sg.finish(st));
     return PBRE_OK;
 }
 

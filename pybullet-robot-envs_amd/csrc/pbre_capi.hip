@@ -92,11 +92,10 @@ __global__ void k_scatter(float* __restrict__ dst, const float* __restrict__ src
 
 static thread_local std::string g_err;      // errors without a ctx (pbre_create): per calling thread (MultiEngine creates its shards from one thread per device)
 
+int pbre::fail(pbre_ctx* c, int code, const char* msg) { (c ? c->err : g_err) = msg; return code; }
+
 extern "C" {
 __attribute__((visibility("hidden"))) void pbre_comm_release(const pbre_ctx* c);      // pbre_comm.hip: the ctx's RCCL communicator, if any
-// pbre_camera.hip (include/pbre_camera.h): the camera's per-ctx record -- a copy of the RobotTable (the engines keep lane tables only) -- and its release
-__attribute__((visibility("hidden"))) CamState* pbre_camera_state_new(const double* robot_table, size_t len);
-__attribute__((visibility("hidden"))) void pbre_camera_state_free(CamState* s);
 }
 
 // ------------------------------------------------------------------ pbre_ctx: the host logic every engine shares
@@ -105,7 +104,6 @@ void pbre_ctx::destroy(pbre_ctx* c) {
     pbre_comm_release(c);
     (void)hipSetDevice(c->device);
     if (c->stream) (void)c->quiesce();        // (a SidePick waits for its candidate streams itself, before the engine's buffers go)
-    pbre_camera_state_free(c->cam); c->cam = nullptr;
     delete c;
 }
 
@@ -298,13 +296,13 @@ int pbre_ctx::read_bad() const {
     if (d_bad) { (void)hipSetDevice(device); (void)hipDeviceSynchronize(); (void)hipMemcpy(&bad, d_bad, sizeof(int), hipMemcpyDeviceToHost); }
     return bad;
 }
-// Fills *v for a render on `abi_stream` (as for pbre_step_device).  host_sync: a host-synchronous render -- all work of the engine is
-// complete on return (then abi_stream must be null).
-int pbre_ctx::cam_view(CamView* v, void* abi_stream, bool host_sync) {
+// Fills *v for a unit's kernels on `abi_stream` (as for pbre_step_device).  host_sync: a host-synchronous call -- all work of the engine
+// is complete on return (then abi_stream must be null).
+int pbre_ctx::state_view(StateView* v, void* abi_stream, bool host_sync) {
     HIPCHK(hipSetDevice(device));
     if (host_sync) HIPCHK(quiesce());
     else if (abi_stream) ext_dirty = true;
-    v->state = state; v->stride = sf; v->n = n; v->obj_lane = lc; v->device = device; v->flags = cfg.flags;
+    v->state = state; v->stride = sf; v->n = n; v->obj_lane = lc; v->flags = cfg.flags;
     v->phys = cfg.phys; v->hull = P.obj_shape == PBRE_SHAPE_HULL ? P.hull : nullptr;
     v->stream = (void*)stream_of(abi_stream);
     return PBRE_OK;
@@ -662,13 +660,6 @@ extern "C" {
 
 int pbre_default_config(pbre_config* cfg, int32_t robot, int32_t task) { return default_config(cfg, robot, task); }
 
-// what the camera asks of a ctx (pbre_camera.hip); *cam: the ctx's slot for the camera's record
-__attribute__((visibility("hidden"))) int pbre_camera_view(pbre_ctx* c, CamView* v, void* stream, int host_sync, CamState** cam) {
-    *cam = c->cam;
-    return c->cam_view(v, stream, host_sync != 0);
-}
-__attribute__((visibility("hidden"))) void pbre_camera_set_error(pbre_ctx* c, const char* msg) { (c ? c->err : g_err) = msg; }
-
 void pbre_destroy(pbre_ctx* c) { pbre_ctx::destroy(c); }
 
 int pbre_create(const pbre_config* cfg, pbre_ctx** out) {
@@ -678,7 +669,7 @@ int pbre_create(const pbre_config* cfg, pbre_ctx** out) {
     pbre_ctx* c = (table_ndof(*cfg) > NJ || cfg->robot_level) ? new_lane_group_engine(*cfg) : new PandaEngine();
     const int rc = c->init(*cfg);
     if (rc != PBRE_OK) { g_err = c->err; pbre_ctx::destroy(c); return rc; }
-    c->cam = pbre_camera_state_new(cfg->robot_table, cfg->robot_table_len);
+    c->readers.set_table(cfg->robot_table, cfg->robot_table_len);      // (the engines keep lane tables only)
     *out = c;
     return PBRE_OK;
 }

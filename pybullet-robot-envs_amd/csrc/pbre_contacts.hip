@@ -94,11 +94,7 @@ __global__ __launch_bounds__(CQ_TPB) void k_contact_query(const CqParams P) {
 
 using namespace pbre;
 
-// pbre_capi.hip: the view the camera uses, and the ctx's record (pbre_scene.hpp: CamState)
-extern "C" __attribute__((visibility("hidden"))) int pbre_camera_view(pbre_ctx* c, CamView* v, void* stream, int host_sync, CamState** cam);
-extern "C" __attribute__((visibility("hidden"))) void pbre_camera_set_error(pbre_ctx* c, const char* msg);
-
-static int fail(pbre_ctx* ctx, int code, const char* msg) { pbre_camera_set_error(ctx, msg); return code; }
+// (the ctx: pbre_engine.hpp -- state_view, fail (pbre_capi.hip) and its record pbre_ctx::readers (pbre_scene.hpp: the RobotTable copy, CqBufs))
 
 static int check_query(pbre_ctx* ctx, const pbre_contact_out* o, float margin) {
     if (!ctx) return fail(nullptr, PBRE_E_ARG, "pbre_contact_query: null ctx");
@@ -109,43 +105,35 @@ static int check_query(pbre_ctx* ctx, const pbre_contact_out* o, float margin) {
 static bool nothing_asked(const pbre_contact_out* o) { return !o->flags && !o->dist && !o->nearest && !o->count && !o->tips; }
 
 // enqueue the kernel on v.stream; the outputs are device pointers (null: skipped)
-static int query_on(pbre_ctx* ctx, CamState* s, const CamView& v, const pbre_contact_out& o, float margin) {
-    if (!s || s->table.empty()) return fail(ctx, PBRE_E_TABLE, "pbre_contact_query: the ctx has no RobotTable");
+static int query_on(pbre_ctx* ctx, const StateView& v, const pbre_contact_out& o, float margin) {
+    Readers& r = ctx->readers;
+    CqBufs& s = r.cq;
+    if (r.table.empty()) return fail(ctx, PBRE_E_TABLE, "pbre_contact_query: the ctx has no RobotTable");
     hipStream_t st = (hipStream_t)v.stream;
-    s->device = v.device;
-    const int ns = s->ns;
-    if (!s->d_cq_table) {                        // header, links, spheres: once per ctx
-        std::vector<float> tab = scene_link_table(*s);
-        const double* t = s->table.data();
+    const int ns = r.ns;
+    if (!s.table) {                              // header, links, spheres: once per ctx
+        std::vector<float> tab = scene_link_table(r);
+        const double* t = r.table.data();
         for (int k = 0; k < ns; k++) {
-            const double* r = t + 24 + s->nl * 40 + k * 8;
-            const float rec[CQ_SPHERE] = {(float)r[0], (float)r[1], (float)r[2], (float)r[3], (float)r[4], (float)r[6], 0.0f, 0.0f};
-            if (!(r[0] >= 0.0 && r[0] < (double)s->nl)) return fail(ctx, PBRE_E_TABLE, "pbre_contact_query: a collision sphere's link index is out of range");
-            if (r[6] > 32.0) return fail(ctx, PBRE_E_TABLE, "pbre_contact_query: more than 32 fingertip slots");
+            const double* q = t + 24 + r.nl * 40 + k * 8;
+            const float rec[CQ_SPHERE] = {(float)q[0], (float)q[1], (float)q[2], (float)q[3], (float)q[4], (float)q[6], 0.0f, 0.0f};
+            if (!(q[0] >= 0.0 && q[0] < (double)r.nl)) return fail(ctx, PBRE_E_TABLE, "pbre_contact_query: a collision sphere's link index is out of range");
+            if (q[6] > 32.0) return fail(ctx, PBRE_E_TABLE, "pbre_contact_query: more than 32 fingertip slots");
             tab.insert(tab.end(), rec, rec + CQ_SPHERE);
         }
-        for (int i = 0; i < s->nl; i++) {        // what scene_fk indexes with: parents before children, joint values inside a record
+        for (int i = 0; i < r.nl; i++) {         // what scene_fk indexes with: parents before children, joint values inside a record
             const float* L = tab.data() + CT_HDR + CT_LINK * i;
             if (!(L[0] < (float)i) || (L[1] != 0.0f && !(L[17] >= 0.0f && L[17] < (float)v.stride)))
                 return fail(ctx, PBRE_E_TABLE, "pbre_contact_query: RobotTable links out of order or a joint index outside the state record");
         }
-        float* d = nullptr;
-        PBRE_CHK_ON(ctx, hipMalloc(&d, tab.size() * sizeof(float)));
-        const hipError_t e = hipMemcpy(d, tab.data(), tab.size() * sizeof(float), hipMemcpyHostToDevice);
-        if (e != hipSuccess) { (void)hipFree(d); return ctx->hip_fail("hipMemcpy", e); }
-        s->d_cq_table = d;
+        PBRE_CHK_ON(ctx, upload_once(s.table, tab));
     }
-    if (v.n > s->cq_cap_n) {
-        PBRE_CHK_ON(ctx, hipDeviceSynchronize());          // (a query in flight on another stream may still use the old buffer)
-        if (s->d_cq_frames) PBRE_CHK_ON(ctx, hipFree(s->d_cq_frames));
-        s->d_cq_frames = nullptr; s->cq_cap_n = 0;
-        PBRE_CHK_ON(ctx, hipMalloc(&s->d_cq_frames, (size_t)std::max(s->nl, 1) * 12 * v.n * sizeof(float)));
-        s->cq_cap_n = v.n;
-    }
+    // (a query in flight on another stream may still use the old buffer)
+    PBRE_CHK_ON(ctx, grow(s.frames, s.cap_frames, (size_t)std::max(r.nl, 1) * 12 * v.n, true));
     CqParams P;
     std::memset(&P, 0, sizeof P);
-    P.tab = s->d_cq_table; P.state = v.state; P.stride = v.stride; P.n = v.n; P.obj_lane = v.obj_lane; P.ns = ns;
-    P.frames = s->d_cq_frames;
+    P.tab = s.table; P.state = v.state; P.stride = v.stride; P.n = v.n; P.obj_lane = v.obj_lane; P.ns = ns;
+    P.frames = s.frames;
     P.margin = margin < 0.0f ? (float)v.phys.contact_margin : margin;
     P.obj_shape = (v.flags & PBRE_F_NO_OBJECT) ? -1 : v.phys.obj_shape;
     for (int k = 0; k < 3; k++) { P.tab_c[k] = (float)v.phys.table_c[k]; P.tab_h[k] = (float)v.phys.table_h[k]; P.obj_h[k] = (float)v.phys.obj_h[k]; }
@@ -165,40 +153,26 @@ int pbre_contact_query_device(pbre_ctx* ctx, const pbre_contact_out* d_out, floa
     int rc = check_query(ctx, d_out, margin);
     if (rc != PBRE_OK) return rc;
     if (nothing_asked(d_out)) return PBRE_OK;
-    CamView v; CamState* s = nullptr;
-    if ((rc = pbre_camera_view(ctx, &v, stream, 0, &s)) != PBRE_OK) return rc;
-    return query_on(ctx, s, v, *d_out, margin);
+    StateView v;
+    if ((rc = ctx->state_view(&v, stream, false)) != PBRE_OK) return rc;
+    return query_on(ctx, v, *d_out, margin);
 }
 
 int pbre_contact_query(pbre_ctx* ctx, const pbre_contact_out* out, float margin) {
     int rc = check_query(ctx, out, margin);
     if (rc != PBRE_OK) return rc;
     if (nothing_asked(out)) return PBRE_OK;
-    CamView v; CamState* s = nullptr;
-    if ((rc = pbre_camera_view(ctx, &v, nullptr, 1, &s)) != PBRE_OK) return rc;
-    if (!s) return fail(ctx, PBRE_E_TABLE, "pbre_contact_query: the ctx has no RobotTable");
-    if (v.n > s->cq_cap_out) {
-        if (s->d_cq_out) PBRE_CHK_ON(ctx, hipFree(s->d_cq_out));
-        s->d_cq_out = nullptr; s->cq_cap_out = 0;
-        PBRE_CHK_ON(ctx, hipMalloc(&s->d_cq_out, (size_t)v.n * 9 * 4));      // flags | dist[3] | nearest[2] | count[2] | tips, 4 bytes each
-        s->cq_cap_out = v.n;
-    }
+    StateView v;
+    if ((rc = ctx->state_view(&v, nullptr, true)) != PBRE_OK) return rc;
     const size_t n = (size_t)v.n;
-    char* b = (char*)s->d_cq_out;
-    pbre_contact_out d;
-    d.flags = out->flags ? (int32_t*)b : nullptr;
-    d.dist = out->dist ? (float*)(b + n * 4) : nullptr;
-    d.nearest = out->nearest ? (int32_t*)(b + n * 16) : nullptr;
-    d.count = out->count ? (int32_t*)(b + n * 24) : nullptr;
-    d.tips = out->tips ? (int32_t*)(b + n * 32) : nullptr;
-    if ((rc = query_on(ctx, s, v, d, margin)) != PBRE_OK) return rc;
     hipStream_t st = (hipStream_t)v.stream;
-    if (out->flags) PBRE_CHK_ON(ctx, hipMemcpyAsync(out->flags, d.flags, n * 4, hipMemcpyDeviceToHost, st));
-    if (out->dist) PBRE_CHK_ON(ctx, hipMemcpyAsync(out->dist, d.dist, n * 12, hipMemcpyDeviceToHost, st));
-    if (out->nearest) PBRE_CHK_ON(ctx, hipMemcpyAsync(out->nearest, d.nearest, n * 8, hipMemcpyDeviceToHost, st));
-    if (out->count) PBRE_CHK_ON(ctx, hipMemcpyAsync(out->count, d.count, n * 8, hipMemcpyDeviceToHost, st));
-    if (out->tips) PBRE_CHK_ON(ctx, hipMemcpyAsync(out->tips, d.tips, n * 4, hipMemcpyDeviceToHost, st));
-    PBRE_CHK_ON(ctx, hipStreamSynchronize(st));
+    Stage sg;                                    // flags | dist[3] | nearest[2] | count[2] | tips, 4 bytes each
+    const int i_flags = sg.add(out->flags, n * 4), i_dist = sg.add(out->dist, n * 12), i_nearest = sg.add(out->nearest, n * 8), i_count = sg.add(out->count, n * 8),
+              i_tips = sg.add(out->tips, n * 4);
+    PBRE_CHK_ON(ctx, sg.begin(ctx->readers.cq.out, ctx->readers.cq.cap_out, st));
+    const pbre_contact_out d = {sg.dev<int32_t>(i_flags), sg.dev<float>(i_dist), sg.dev<int32_t>(i_nearest), sg.dev<int32_t>(i_count), sg.dev<int32_t>(i_tips)};
+    if ((rc = query_on(ctx, v, d, margin)) != PBRE_OK) return rc;
+    PBRE_CHK_ON(ctx, sg.finish(st));
     return PBRE_OK;
 }
 

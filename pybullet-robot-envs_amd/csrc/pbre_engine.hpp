@@ -9,6 +9,7 @@
 #include <string>
 #include "pbre_devmem.hpp"
 #include "pbre_host.hpp"
+#include "pbre_scene.hpp"
 
 // the one HIP error check of the library, with an engine `eng`; HIPCHK is its spelling inside a method of an engine.  (Set-up helpers that
 // hand a hipError_t on to such a check -- alloc_buf, lane_alloc, SidePick::create -- test their calls themselves.)
@@ -16,12 +17,11 @@
 #define HIPCHK(call) PBRE_CHK_ON(this, call)
 
 namespace pbre {
-// What the camera (pbre_camera.hip, include/pbre_camera.h) reads of an engine -- it writes none of it: the state records [n][stride] floats
-// on the device (object pose at float obj_lane of a record), the scene, the hull table (null without one; its piece directory is in
-// its header, pbre_tables.hpp) and the stream the render goes to.
-struct CamState;      // the camera's own buffers: pbre_ctx::cam
-struct CamView {
-    const float* state; int stride, n, obj_lane, device, flags;
+// What a unit that reads an engine's state without stepping it gets (the camera, the contact query, the kinematics query) -- it writes
+// none of it: the state records [n][stride] floats on the device (object pose at float obj_lane of a record), the scene, the hull table
+// (null without one; its piece directory is in its header, pbre_tables.hpp) and the stream the unit's kernels go to.
+struct StateView {
+    const float* state; int stride, n, obj_lane, flags;
     pbre_physics phys;
     const float* hull;
     void* stream;         // a hipStream_t
@@ -50,7 +50,7 @@ struct pbre_ctx {
     bool stale_snapshot = false;              // ... and a later scene change invalidated it
     bool ext_dirty = false;                   // a step was enqueued on a caller-supplied stream since the last quiesce()
     std::string err;
-    pbre::CamState* cam = nullptr;            // the camera's RobotTable copy, visual list and scene buffer (pbre_camera.hip owns it)
+    pbre::Readers readers;                    // the RobotTable copy and the buffers of the units that read the state (pbre_scene.hpp)
 
     virtual ~pbre_ctx() {}
     // the only way an engine is deleted: device set, its streams drained, then its owners release (also after a failed init)
@@ -83,7 +83,7 @@ struct pbre_ctx {
     int set_physics(const pbre_physics* phys);
     int set_object_hull(const double* verts, int32_t n_verts);
     int timing(double* out, int32_t cnt) const;
-    int cam_view(pbre::CamView* v, void* stream, bool host_sync);
+    int state_view(pbre::StateView* v, void* stream, bool host_sync);
 
     // ---- hooks of the shared logic
     virtual hipError_t state_changed() = 0;   // the records or the scene were changed by something other than a step
@@ -116,5 +116,6 @@ struct pbre_ctx {
 };
 
 namespace pbre {
+int fail(pbre_ctx* c, int code, const char* msg);             // pbre_capi.hip: the text to c->err, or without a ctx to the calling thread's slot; returns code
 pbre_ctx* new_lane_group_engine(const pbre_config& cfg);      // pbre_wide.hip: the implementation for a robot of more than 9 DoF / the robot level
 }

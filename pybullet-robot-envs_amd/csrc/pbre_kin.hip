@@ -104,11 +104,7 @@ __global__ __launch_bounds__(KQ_TPB) void k_kin_rows(const float* __restrict__ t
 
 using namespace pbre;
 
-// pbre_capi.hip: the view the camera uses, and the ctx's record (pbre_scene.hpp: CamState)
-extern "C" __attribute__((visibility("hidden"))) int pbre_camera_view(pbre_ctx* c, CamView* v, void* stream, int host_sync, CamState** cam);
-extern "C" __attribute__((visibility("hidden"))) void pbre_camera_set_error(pbre_ctx* c, const char* msg);
-
-static int fail(pbre_ctx* ctx, int code, const char* msg) { pbre_camera_set_error(ctx, msg); return code; }
+// (the ctx: pbre_engine.hpp -- state_view, fail (pbre_capi.hip) and its record pbre_ctx::readers (pbre_scene.hpp: the RobotTable copy, KinBufs))
 
 static int check_query(pbre_ctx* ctx, const pbre_kin_query_t* q) {
     if (!ctx) return fail(nullptr, PBRE_E_ARG, "pbre_kin_query: null ctx");
@@ -120,10 +116,11 @@ static int check_query(pbre_ctx* ctx, const pbre_kin_query_t* q) {
 static bool nothing_asked(const pbre_kin_query_t* q) { return !q->pose && !q->vel && !q->jac && !q->mass && !q->tau; }
 
 // the checks that need the table; fills the link list and the Jacobian's link
-static int check_table(pbre_ctx* ctx, const CamState* s, const pbre_kin_query_t& q, int stride, KqParams& P) {
-    if (!s || s->table.empty()) return fail(ctx, PBRE_E_TABLE, "pbre_kin_query: the ctx has no RobotTable");
-    const double* t = s->table.data();
-    const int nl = s->nl, nd = s->ndof;
+static int check_table(pbre_ctx* ctx, const pbre_kin_query_t& q, int stride, KqParams& P) {
+    const Readers& s = ctx->readers;
+    if (s.table.empty()) return fail(ctx, PBRE_E_TABLE, "pbre_kin_query: the ctx has no RobotTable");
+    const double* t = s.table.data();
+    const int nl = s.nl, nd = s.ndof;
     if (t[18] == 0.0) return fail(ctx, PBRE_E_UNSUPPORTED, "pbre_kin_query: a RobotTable with fixed_base = 0 (a free-floating base) is not supported");
     if (nl > kin::MAX_LINKS || nd > kin::MAX_DOF || nd < 0) return fail(ctx, PBRE_E_UNSUPPORTED, "pbre_kin_query: more than 128 links or 64 DoF");
     if (q.n_links > nl) return fail(ctx, PBRE_E_ARG, "pbre_kin_query: n_links is above the table's link count");
@@ -143,35 +140,23 @@ static int check_table(pbre_ctx* ctx, const CamState* s, const pbre_kin_query_t&
 }
 
 // enqueue the kernels on v.stream; the outputs (and qdd) are device pointers (null: skipped)
-static int query_on(pbre_ctx* ctx, CamState* s, const CamView& v, const pbre_kin_query_t& q, KqParams& P) {
+static int query_on(pbre_ctx* ctx, const StateView& v, const pbre_kin_query_t& q, KqParams& P) {
     hipStream_t st = (hipStream_t)v.stream;
-    s->device = v.device;
-    const int nl = s->nl, nd = s->ndof, n = v.n;
+    const Readers& r = ctx->readers;
+    KinBufs& s = ctx->readers.kin;
+    const int nl = r.nl, nd = r.ndof, n = v.n;
     const bool links = q.n_links > 0 && (q.pose || q.vel), vel = links && q.vel;
     const bool want_jac = q.jac && nd > 0, want_mass = q.mass && nd > 0, want_tau = q.tau && nd > 0;
     if (!links && !want_jac && !want_mass && !want_tau) return PBRE_OK;
-    if (!s->d_kin_table) {                       // once per ctx: the RobotTable never changes
-        const std::vector<float> tab = kin::kin_table(s->table.data());
-        float* d = nullptr;
-        PBRE_CHK_ON(ctx, hipMalloc(&d, tab.size() * sizeof(float)));
-        const hipError_t e = hipMemcpy(d, tab.data(), tab.size() * sizeof(float), hipMemcpyHostToDevice);
-        if (e != hipSuccess) { (void)hipFree(d); return ctx->hip_fail("hipMemcpy", e); }
-        s->d_kin_table = d;
-    }
+    if (!s.table) PBRE_CHK_ON(ctx, upload_once(s.table, kin::kin_table(r.table.data())));      // once per ctx: the RobotTable never changes
     // column buffers of this query: frames | composites | wrenches | staging (jac and mass use it one after the other)
     const size_t N = (size_t)n;
     const size_t f_frames = (size_t)std::max(nl, 1) * kin::KC * N, f_comp = want_mass ? (size_t)nl * kin::KCOMP * N : 0, f_wr = want_tau ? (size_t)nl * kin::KWR * N : 0;
     const size_t f_stage = std::max(want_jac ? (size_t)6 * nd : 0, want_mass ? (size_t)nd * nd : 0) * N;
-    const size_t need = f_frames + f_comp + f_wr + f_stage;
-    if (need > s->kin_cap_cols) {
-        PBRE_CHK_ON(ctx, hipDeviceSynchronize());          // (a query in flight on another stream may still use the old buffer)
-        if (s->d_kin_cols) PBRE_CHK_ON(ctx, hipFree(s->d_kin_cols));
-        s->d_kin_cols = nullptr; s->kin_cap_cols = 0;
-        PBRE_CHK_ON(ctx, hipMalloc(&s->d_kin_cols, need * sizeof(float)));
-        s->kin_cap_cols = need;
-    }
-    P.tab = s->d_kin_table; P.state = v.state; P.stride = v.stride; P.W = (v.stride - 16) / 2; P.n = n; P.nd = nd;
-    P.cols = s->d_kin_cols; P.comp = P.cols + f_frames; P.wr = P.comp + f_comp; P.stage = P.wr + f_wr;
+    // (a query in flight on another stream may still use the old buffer)
+    PBRE_CHK_ON(ctx, grow(s.cols, s.cap_cols, f_frames + f_comp + f_wr + f_stage, true));
+    P.tab = s.table; P.state = v.state; P.stride = v.stride; P.W = (v.stride - 16) / 2; P.n = n; P.nd = nd;
+    P.cols = s.cols; P.comp = P.cols + f_frames; P.wr = P.comp + f_comp; P.stage = P.wr + f_wr;
     P.qdd = q.qdd; P.g_up = (float)(-v.phys.gravity_z);
     P.n_links = q.n_links; P.at_com = q.at_com; P.jac_at_com = q.jac_at_com;
     for (int k = 0; k < 3; k++) P.jac_point[k] = q.jac_point[k];
@@ -183,7 +168,7 @@ static int query_on(pbre_ctx* ctx, CamState* s, const CamView& v, const pbre_kin
     if (links) hipLaunchKernelGGL(k_kin_links, grid, block, 0, st, P);
     if (want_jac) {
         unsigned long long dofs = 0;
-        const double* t = s->table.data();
+        const double* t = r.table.data();
         for (int i = P.jac_link; i >= 0; i = (int)t[24 + i * 40]) if (t[24 + i * 40 + 1] != 0.0) dofs |= 1ull << (int)t[24 + i * 40 + 33];
         hipLaunchKernelGGL(k_kin_jac, grid, block, 0, st, P);
         const int K = 6 * nd;
@@ -204,52 +189,36 @@ extern "C" {
 int pbre_kin_query_device(pbre_ctx* ctx, const pbre_kin_query_t* q, void* stream) {
     int rc = check_query(ctx, q);
     if (rc != PBRE_OK) return rc;
-    CamView v; CamState* s = nullptr;
-    if ((rc = pbre_camera_view(ctx, &v, stream, 0, &s)) != PBRE_OK) return rc;
+    StateView v;
+    if ((rc = ctx->state_view(&v, stream, false)) != PBRE_OK) return rc;
     KqParams P;
     std::memset(&P, 0, sizeof P);
-    if ((rc = check_table(ctx, s, *q, v.stride, P)) != PBRE_OK) return rc;
+    if ((rc = check_table(ctx, *q, v.stride, P)) != PBRE_OK) return rc;
     if (nothing_asked(q)) return PBRE_OK;
-    return query_on(ctx, s, v, *q, P);
+    return query_on(ctx, v, *q, P);
 }
 
 int pbre_kin_query(pbre_ctx* ctx, const pbre_kin_query_t* q) {
     int rc = check_query(ctx, q);
     if (rc != PBRE_OK) return rc;
-    CamView v; CamState* s = nullptr;
-    if ((rc = pbre_camera_view(ctx, &v, nullptr, 1, &s)) != PBRE_OK) return rc;
+    StateView v;
+    if ((rc = ctx->state_view(&v, nullptr, true)) != PBRE_OK) return rc;
     KqParams P;
     std::memset(&P, 0, sizeof P);
-    if ((rc = check_table(ctx, s, *q, v.stride, P)) != PBRE_OK) return rc;
+    if ((rc = check_table(ctx, *q, v.stride, P)) != PBRE_OK) return rc;
     if (nothing_asked(q)) return PBRE_OK;
-    const size_t n = (size_t)v.n, nd = (size_t)s->ndof, nlq = (size_t)q->n_links;
-    // pose | vel | jac | mass | tau | qdd, floats per env
-    const size_t f_pose = q->pose ? nlq * 7 : 0, f_vel = q->vel ? nlq * 6 : 0, f_jac = q->jac ? 6 * nd : 0, f_mass = q->mass ? nd * nd : 0, f_tau = q->tau ? nd : 0;
-    const size_t f_qdd = (q->qdd && q->tau) ? nd : 0;
-    const size_t need = std::max<size_t>((f_pose + f_vel + f_jac + f_mass + f_tau + f_qdd) * n * sizeof(float), 4);
-    if (need > s->kin_cap_out) {
-        if (s->d_kin_out) PBRE_CHK_ON(ctx, hipFree(s->d_kin_out));
-        s->d_kin_out = nullptr; s->kin_cap_out = 0;
-        PBRE_CHK_ON(ctx, hipMalloc(&s->d_kin_out, need));
-        s->kin_cap_out = need;
-    }
-    float* b = (float*)s->d_kin_out;
-    pbre_kin_query_t d = *q;
-    d.pose = f_pose ? b : nullptr; b += f_pose * n;
-    d.vel = f_vel ? b : nullptr; b += f_vel * n;
-    d.jac = f_jac ? b : nullptr; b += f_jac * n;
-    d.mass = f_mass ? b : nullptr; b += f_mass * n;
-    d.tau = f_tau ? b : nullptr; b += f_tau * n;
-    d.qdd = f_qdd ? b : nullptr;
+    const size_t nd = (size_t)ctx->readers.ndof, nlq = (size_t)q->n_links, rec = (size_t)v.n * sizeof(float);
     hipStream_t st = (hipStream_t)v.stream;
-    if (f_qdd) PBRE_CHK_ON(ctx, hipMemcpyAsync(b, q->qdd, f_qdd * n * sizeof(float), hipMemcpyHostToDevice, st));
-    if ((rc = query_on(ctx, s, v, d, P)) != PBRE_OK) return rc;
-    if (f_pose) PBRE_CHK_ON(ctx, hipMemcpyAsync(q->pose, d.pose, f_pose * n * sizeof(float), hipMemcpyDeviceToHost, st));
-    if (f_vel) PBRE_CHK_ON(ctx, hipMemcpyAsync(q->vel, d.vel, f_vel * n * sizeof(float), hipMemcpyDeviceToHost, st));
-    if (f_jac) PBRE_CHK_ON(ctx, hipMemcpyAsync(q->jac, d.jac, f_jac * n * sizeof(float), hipMemcpyDeviceToHost, st));
-    if (f_mass) PBRE_CHK_ON(ctx, hipMemcpyAsync(q->mass, d.mass, f_mass * n * sizeof(float), hipMemcpyDeviceToHost, st));
-    if (f_tau) PBRE_CHK_ON(ctx, hipMemcpyAsync(q->tau, d.tau, f_tau * n * sizeof(float), hipMemcpyDeviceToHost, st));
-    PBRE_CHK_ON(ctx, hipStreamSynchronize(st));
+    Stage sg;                                    // pose | vel | jac | mass | tau | qdd; what is not asked for takes no space
+    auto add = [&](const void* host, size_t floats, bool in) { return sg.add(host, host ? floats * rec : 0, in); };
+    const int i_pose = add(q->pose, nlq * 7, false), i_vel = add(q->vel, nlq * 6, false), i_jac = add(q->jac, 6 * nd, false), i_mass = add(q->mass, nd * nd, false),
+              i_tau = add(q->tau, nd, false), i_qdd = add(q->tau ? q->qdd : nullptr, nd, true);
+    PBRE_CHK_ON(ctx, sg.begin(ctx->readers.kin.out, ctx->readers.kin.cap_out, st));
+    pbre_kin_query_t d = *q;
+    d.pose = sg.dev<float>(i_pose); d.vel = sg.dev<float>(i_vel); d.jac = sg.dev<float>(i_jac); d.mass = sg.dev<float>(i_mass); d.tau = sg.dev<float>(i_tau);
+    d.qdd = sg.dev<float>(i_qdd);
+    if ((rc = query_on(ctx, v, d, P)) != PBRE_OK) return rc;
+    PBRE_CHK_ON(ctx, sg.finish(st));
     return PBRE_OK;
 }
 

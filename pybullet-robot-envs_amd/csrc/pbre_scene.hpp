@@ -1,40 +1,50 @@
-// pbre_scene.hpp -- what the units that read an engine's state records without stepping them share: the camera (pbre_camera.hip) and the
-// contact query (pbre_contacts.hip).  The per-ctx record with the one host copy of the RobotTable (pbre_ctx::cam), the float link table
-// both upload, and the one forward-kinematics loop both kernels run.
+// pbre_scene.hpp -- what the units that read an engine's state records without stepping them share: the camera (pbre_camera.hip), the
+// contact query (pbre_contacts.hip) and the kinematics query (pbre_kin.hip).  The per-ctx record (pbre_ctx::readers): the one host copy of
+// the RobotTable and each unit's own buffers; the float link table the camera and the contact query upload, and the one
+// forward-kinematics loop both their kernels run.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <vector>
+#include "pbre_devwork.hpp"
 
 namespace pbre {
 
 constexpr int CT_HDR = 16, CT_LINK = 20;        // device table: [0] n_links [1] n_prims [2..4] base position [5..13] base rotation; links; primitives / spheres
 constexpr int CQ_SPHERE = 8;                    // contact query: a sphere is link | centre[3] | radius | fingertip slot + 1 | 0 | 0
 
-struct CamState {
-    std::vector<double> table;                  // the RobotTable (include/pbre.h)
-    int nl = 0, ns = 0, ndof = 0;
+// Each unit keeps buffers of its own, so that queries on different streams cannot race.  A capacity follows the buffer it describes
+// (grow, pbre_devwork.hpp); `out` is the block of the host-buffer variant (Stage).
+struct CamBufs {
     std::vector<float> visuals;                 // the caller's list (12 floats each); empty: the collision spheres
     int nprims = 0;
     bool dirty = true;                          // the device table is older than the list
-    int device = -1;
-    float *d_table = nullptr, *d_frames = nullptr, *d_scene = nullptr, *d_views = nullptr;
-    int cap_n = 0, cap_prims = -1;
-    size_t cap_table = 0;
-    void* d_img = nullptr; size_t cap_img = 0;  // images of the host-buffer render
-    // the contact query's (pbre_contacts.hip): links + collision spheres (uploaded once: the RobotTable never changes), link frames, and
-    // the outputs of the host-buffer query
-    float *d_cq_table = nullptr, *d_cq_frames = nullptr;
-    void* d_cq_out = nullptr;
-    int cq_cap_n = 0, cq_cap_out = 0;
-    // the kinematics query's (pbre_kin.hip), its own so that a contact query on another stream cannot race with it: the link table with
-    // masses and inertias (uploaded once), the column buffers of one query, and the outputs of the host-buffer query
-    float *d_kin_table = nullptr, *d_kin_cols = nullptr;
-    void* d_kin_out = nullptr;
-    size_t kin_cap_cols = 0, kin_cap_out = 0;
+    DevBuf<float> table; size_t cap_table = 0;
+    DevBuf<float> work; size_t cap_work = 0;    // of one render: link frames | scene | per-env views
+    DevBuf<char> out; size_t cap_out = 0;
+};
+struct CqBufs {
+    DevBuf<float> table;                        // links + collision spheres, uploaded once: the RobotTable never changes
+    DevBuf<float> frames; size_t cap_frames = 0;
+    DevBuf<char> out; size_t cap_out = 0;
+};
+struct KinBufs {
+    DevBuf<float> table;                        // the link table with masses and inertias, uploaded once
+    DevBuf<float> cols; size_t cap_cols = 0;    // the column buffers of one query
+    DevBuf<char> out; size_t cap_out = 0;
+};
+struct Readers {
+    std::vector<double> table;                  // the RobotTable (include/pbre.h); empty: the ctx was made without a valid one
+    int nl = 0, ns = 0, ndof = 0;
+    CamBufs cam; CqBufs cq; KinBufs kin;
+    void set_table(const double* t, size_t len) {
+        if (!t || len < 24 || t[0] != 1346523717.0) return;
+        const int l = (int)t[2], sp = (int)t[5];
+        if (l >= 0 && sp >= 0 && len >= (size_t)(24 + l * 40 + sp * 8)) { table.assign(t, t + 24 + l * 40 + sp * 8); nl = l; ns = sp; ndof = (int)t[3]; }
+    }
 };
 
 // header and links of the device table (see CT_HDR), from the RobotTable
-inline std::vector<float> scene_link_table(const CamState& s) {
+inline std::vector<float> scene_link_table(const Readers& s) {
     const double* t = s.table.data();
     std::vector<float> out(CT_HDR + (size_t)CT_LINK * s.nl, 0.0f);
     out[0] = (float)s.nl;

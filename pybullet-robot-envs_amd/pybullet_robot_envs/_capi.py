@@ -524,6 +524,20 @@ class Engine:
         self._chk(self.lib.pbre_kernel_info(self._ctx, info, C.c_int32(16)))
         return list(info)
 
+    def _outputs(self, who, want, out):
+        """The arrays of a call that fills buffers it is handed: want is a list of (name, asked for, shape, dtype name).  Returns the
+        result dict, each array's address by name, and for out="torch" the device and the stream argument of the `_device` entry point
+        (None, None for out="numpy": the host entry point is the one to call)."""
+        if out == "torch":
+            import torch
+            dev = torch.device("cuda", int(self.cfg.device_id))
+            res = {k: torch.empty(shape, dtype=getattr(torch, dt), device=dev) for k, on, shape, dt in want if on}
+            return res, {k: t.data_ptr() for k, t in res.items()}, dev, C.c_void_p(torch_stream(dev))
+        if out != "numpy":
+            raise ValueError("%s: out must be 'numpy' or 'torch'" % who)
+        res = {k: np.empty(shape, dt) for k, on, shape, dt in want if on}
+        return res, {k: a.ctypes.data for k, a in res.items()}, None, None
+
     # ---- the camera (include/pbre_camera.h; csrc/pbre_camera.hip) ----
     def _need_camera(self):
         if not hasattr(self.lib, "pbre_camera_render"):
@@ -577,29 +591,12 @@ class Engine:
         shape = (self.num_envs, int(cam.height), int(cam.width))
         if shape[1] < 1 or shape[2] < 1 or shape[0] * shape[1] * shape[2] > 2 ** 31 - 1:      # (the library says why; allocate nothing)
             self._chk(self.lib.pbre_camera_render(self._ctx, C.byref(cam), None, None, None))
-        res = {}
-        if out == "torch":
-            import torch
-            dev = torch.device("cuda", int(self.cfg.device_id))
-            if depth:
-                res["depth"] = torch.empty(shape, dtype=torch.float32, device=dev)
-            if seg:
-                res["seg"] = torch.empty(shape, dtype=torch.int32, device=dev)
-            if rgb:
-                res["rgba"] = torch.empty(shape + (4,), dtype=torch.uint8, device=dev)
-            ptr = lambda k: C.c_void_p(res[k].data_ptr()) if k in res else None
-            self._chk(self.lib.pbre_camera_render_device(self._ctx, C.byref(cam), ptr("depth"), ptr("seg"), ptr("rgba"), C.c_void_p(torch_stream(dev))))
-            return res
-        if out != "numpy":
-            raise ValueError("render: out must be 'numpy' or 'torch'")
-        if depth:
-            res["depth"] = np.empty(shape, np.float32)
-        if seg:
-            res["seg"] = np.empty(shape, np.int32)
-        if rgb:
-            res["rgba"] = np.empty(shape + (4,), np.uint8)
-        ptr = lambda k: _fp(res[k]) if k in res else None
-        self._chk(self.lib.pbre_camera_render(self._ctx, C.byref(cam), ptr("depth"), ptr("seg"), ptr("rgba")))
+        want = [("depth", depth, shape, "float32"), ("seg", seg, shape, "int32"), ("rgba", rgb, shape + (4,), "uint8")]
+        res, at, _, stream = self._outputs("render", want, out)
+        if stream is not None:
+            self._chk(self.lib.pbre_camera_render_device(self._ctx, C.byref(cam), at.get("depth"), at.get("seg"), at.get("rgba"), stream))
+        else:
+            self._chk(self.lib.pbre_camera_render(self._ctx, C.byref(cam), at.get("depth"), at.get("seg"), at.get("rgba")))
         return res
 
     # ---- the contact query (include/pbre_contacts.h; csrc/pbre_contacts.hip) ----
@@ -618,23 +615,12 @@ class Engine:
         want = [("flags", flags, (n,), "int32"), ("dist", dist, (n, 3), "float32"), ("nearest", nearest, (n, 2), "int32"),
                 ("count", count, (n, 2), "int32"), ("tips", tips, (n,), "int32")]
         mg = C.c_float(-1.0 if margin is None else float(margin))
-        res, o = {}, ContactOut()
-        if out == "torch":
-            import torch
-            dev = torch.device("cuda", int(self.cfg.device_id))
-            for k, on, shape, dt in want:
-                if on:
-                    res[k] = torch.empty(shape, dtype=getattr(torch, dt), device=dev)
-                    setattr(o, k, res[k].data_ptr())
-            self._chk(self.lib.pbre_contact_query_device(self._ctx, C.byref(o), mg, C.c_void_p(torch_stream(dev))))
-            return res
-        if out != "numpy":
-            raise ValueError("contact_query: out must be 'numpy' or 'torch'")
-        for k, on, shape, dt in want:
-            if on:
-                res[k] = np.empty(shape, dt)
-                setattr(o, k, res[k].ctypes.data)
-        self._chk(self.lib.pbre_contact_query(self._ctx, C.byref(o), mg))
+        res, at, _, stream = self._outputs("contact_query", want, out)
+        o = ContactOut(**at)
+        if stream is not None:
+            self._chk(self.lib.pbre_contact_query_device(self._ctx, C.byref(o), mg, stream))
+        else:
+            self._chk(self.lib.pbre_contact_query(self._ctx, C.byref(o), mg))
         return res
 
     # ---- the kinematics / dynamics query (include/pbre_kin.h; csrc/pbre_kin.hip) ----
@@ -651,46 +637,33 @@ class Engine:
         if not hasattr(self.lib, "pbre_kin_query"):
             raise RuntimeError("kin_query: this library has no kinematics query (no pbre_kin_query symbol; the host emulation library "
                                "has none -- compute from get_state() on the host instead)")
-        if out not in ("numpy", "torch"):
-            raise ValueError("kin_query: out must be 'numpy' or 'torch'")
         n, nd = self.num_envs, self.ndof
         if links is None:
             links = np.arange(int(self._table[2]), dtype=np.int32) if (pose or vel) else np.zeros(0, np.int32)
         links = np.ascontiguousarray(np.asarray(links).reshape(-1), dtype=np.int32)
         nlq = len(links)
-        want = [("pose", pose and nlq > 0, (n, nlq, 7)), ("vel", vel and nlq > 0, (n, nlq, 6)), ("jac", jac, (n, 6, nd)), ("mass", mass, (n, nd, nd)),
-                ("tau", tau, (n, nd))]
-        o = KinQuery()
+        want = [("pose", pose and nlq > 0, (n, nlq, 7), "float32"), ("vel", vel and nlq > 0, (n, nlq, 6), "float32"), ("jac", jac, (n, 6, nd), "float32"),
+                ("mass", mass, (n, nd, nd), "float32"), ("tau", tau, (n, nd), "float32")]
+        res, at, dev, stream = self._outputs("kin_query", want, out)
+        o = KinQuery(**at)
         o.links, o.n_links = (links.ctypes.data if nlq else None), nlq
         o.at_com, o.jac_at_com = int(bool(at_com)), int(bool(jac_at_com))
         o.jac_link = -1 if jac_link is None else int(jac_link)
         for k in range(3):
             o.jac_point[k] = float(jac_point[k])
-        res = {}
-        if out == "torch":
-            import torch
-            dev = torch.device("cuda", int(self.cfg.device_id))
-            if qdd is not None and tau:
-                qdd = torch.as_tensor(qdd, dtype=torch.float32, device=dev).contiguous()      # (a host array: uploaded on torch's current stream)
-                if tuple(qdd.shape) != (n, nd):
-                    raise ValueError("kin_query: qdd must have shape (%d, %d)" % (n, nd))
-                o.qdd = qdd.data_ptr()
-            for k, on, shape in want:
-                if on:
-                    res[k] = torch.empty(shape, dtype=torch.float32, device=dev)
-                    setattr(o, k, res[k].data_ptr())
-            self._chk(self.lib.pbre_kin_query_device(self._ctx, C.byref(o), C.c_void_p(torch_stream(dev))))
-            return res
         if qdd is not None and tau:
-            qdd = np.ascontiguousarray(qdd, dtype=np.float32)
-            if qdd.shape != (n, nd):
+            if dev is not None:
+                import torch
+                qdd = torch.as_tensor(qdd, dtype=torch.float32, device=dev).contiguous()      # (a host array: uploaded on torch's current stream)
+            else:
+                qdd = np.ascontiguousarray(qdd, dtype=np.float32)
+            if tuple(qdd.shape) != (n, nd):
                 raise ValueError("kin_query: qdd must have shape (%d, %d)" % (n, nd))
-            o.qdd = qdd.ctypes.data
-        for k, on, shape in want:
-            if on:
-                res[k] = np.empty(shape, np.float32)
-                setattr(o, k, res[k].ctypes.data)
-        self._chk(self.lib.pbre_kin_query(self._ctx, C.byref(o)))
+            o.qdd = qdd.data_ptr() if dev is not None else qdd.ctypes.data
+        if stream is not None:
+            self._chk(self.lib.pbre_kin_query_device(self._ctx, C.byref(o), stream))
+        else:
+            self._chk(self.lib.pbre_kin_query(self._ctx, C.byref(o)))
         return res
 
 

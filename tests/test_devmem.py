@@ -1,6 +1,8 @@
 """The move-only owners of the engines' device resources (csrc/pbre_devmem.hpp), host only: a stand-alone program compiles the header
 against counting stand-ins of hipMalloc / hipFree / the event and stream calls and checks construction, move, release on an early
-return out of a set-up function, and double release -- under AddressSanitizer and UBSan, so a leak or a double free fails the run."""
+return out of a set-up function, and double release; then grow, upload_once and Stage of csrc/pbre_devwork.hpp (the buffers of the
+units that read the state, and the slice layout of their host-buffer variants) -- under AddressSanitizer and UBSan, so a leak or a
+double free fails the run."""
 import os
 import shutil
 import subprocess

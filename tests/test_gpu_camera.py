@@ -216,6 +216,44 @@ def test_render_is_read_only_and_ordered(pushed, panda):
         assert t[k].cpu().numpy().tobytes() == h[k].tobytes()
 
 
+def test_buffers_regrow(hip_lib, panda):
+    """One engine renders 8 x 6, then -- with a longer visual list -- 33 x 17 (561 pixels: two full strips and one of 49), then 8 x 6 again:
+    the device table, the scene buffer and the host variant's block grow in between.  Each image is, byte for byte, that of a fresh engine
+    whose first render it is.  131 envs of the contact query's crafted records."""
+    import contact_scenes as cs
+    st = cs.panda_states(panda)
+    vis = default_visuals(panda["table"])
+    assert len(st) == 131 and len(vis) > 4
+
+    def fresh(visuals):
+        e = _capi.Engine(panda["table"], task=_capi.TASK_PUSH, num_envs=len(st), lib=hip_lib)
+        e.reset()
+        e.set_state(st)
+        e.set_visuals(visuals)
+        return e
+
+    eng = fresh(vis[:4])
+    try:
+        steps = [(8, 6, None), (33, 17, vis), (8, 6, None)]
+        got = []
+        for W, H, longer in steps:
+            if longer is not None:
+                eng.set_visuals(longer)
+            got.append(eng.render(_cams(eng, W, H)[0]))
+        assert got[1]["depth"].shape == (131, 17, 33) and len(np.unique(got[1]["seg"])) >= 4
+        assert got[0]["seg"].tobytes() != got[2]["seg"].tobytes(), "the longer list changed nothing the camera sees"
+        for (W, H, _), visuals, g in zip(steps, (vis[:4], vis, vis), got):
+            one = fresh(visuals)
+            try:
+                want = one.render(_cams(one, W, H)[0])
+            finally:
+                one.close()
+            for k in ("depth", "seg", "rgba"):
+                assert g[k].shape == want[k].shape and g[k].tobytes() == want[k].tobytes(), (W, H, k)
+    finally:
+        eng.close()
+
+
 def test_task_env_render(hip_lib):
     from pybullet_robot_envs.envs.panda_envs.panda_push_gym_env import pandaPushGymEnv
     env = pandaPushGymEnv(num_envs=2)

@@ -118,6 +118,27 @@ def test_no_object(hip_lib, panda, panda_set):
         eng.close()
 
 
+def test_buffers_regrow(hip_lib, panda, panda_set):
+    """out="torch" on a fresh engine (no block of the host variant yet), then the host call, then out="torch" again: the same bytes"""
+    import torch
+    eng = _capi.Engine(panda["table"], task=_capi.TASK_PUSH, num_envs=len(panda_set), lib=hip_lib)
+    try:
+        eng.reset()
+        eng.set_state(panda_set)
+        t1 = eng.contact_query(out="torch")
+        torch.cuda.synchronize()
+        t1 = {k: v.cpu().numpy() for k, v in t1.items()}
+        host = eng.contact_query()
+        t2 = eng.contact_query(out="torch")
+        torch.cuda.synchronize()
+        assert set(t1) == set(host) == set(t2) == {"flags", "dist", "nearest", "count", "tips"} and set(host["flags"]) >= {0, 1, 2, 5}
+        for k, v in host.items():
+            assert v.shape == t1[k].shape and v.dtype == t1[k].dtype
+            assert v.tobytes() == t1[k].tobytes() and v.tobytes() == t2[k].cpu().numpy().tobytes(), k
+    finally:
+        eng.close()
+
+
 def _other_engine(name, hip_lib, n):
     if name == "icub":
         return parity.make_icub_pair(_capi.Engine, hip_lib, n, task=0, control_arm="l", use_ik=1)[0]

@@ -71,6 +71,29 @@ def test_panda_push(pushed, panda, panda_set, hip_lib):
         one.close()
 
 
+def test_buffers_regrow(hip_lib, panda, panda_set):
+    """The column buffer and the host variant's block grow from call to call on one engine (tau, then the Jacobian, then M, then
+    everything); each result is, byte for byte, that of a second fresh engine whose first call asked for everything."""
+    st, qdd = panda_set
+    engs = [_capi.Engine(panda["table"], task=_capi.TASK_PUSH, num_envs=len(st), lib=hip_lib) for _ in range(2)]
+    try:
+        for e in engs:
+            e.reset()
+            e.set_state(st)
+        grown, first = engs
+        only = lambda k: {x: x == k for x in ("pose", "vel", "jac", "mass", "tau")}
+        got = [grown.kin_query(qdd=qdd, **only(k)) for k in ("tau", "jac", "mass")] + [grown.kin_query(qdd=qdd)]
+        want = first.kin_query(qdd=qdd)
+        assert [set(g) for g in got] == [{"tau"}, {"jac"}, {"mass"}, {"pose", "vel", "jac", "mass", "tau"}] and set(want) == set(got[3])
+        assert np.abs(want["tau"]).max() > 1.0 and np.abs(want["jac"]).max() > 0.1
+        for g in got:
+            for k, v in g.items():
+                assert v.shape == want[k].shape and v.tobytes() == want[k].tobytes(), k
+    finally:
+        for e in engs:
+            e.close()
+
+
 def _other_engine(name, hip_lib, n):
     if name == "icub":
         return parity.make_icub_pair(_capi.Engine, hip_lib, n, task=0, control_arm="l", use_ik=1)[0]
