@@ -1,5 +1,5 @@
 // pbre_scene.hpp -- what the units that read an engine's state records without stepping them share: the camera (pbre_camera.hip), the
-// contact query (pbre_contacts.hip) and the kinematics query (pbre_kin.hip).  The per-ctx record (pbre_ctx::readers): the one host copy of
+// contact query (pbre_contacts.hip), the kinematics query (pbre_kin.hip) and the inverse-kinematics query (pbre_ik.hip).  The per-ctx record (pbre_ctx::readers): the one host copy of
 // the RobotTable and each unit's own buffers; the float link table the camera and the contact query upload, and the one
 // forward-kinematics loop both their kernels run.
 #pragma once
@@ -32,10 +32,14 @@ struct KinBufs {
     DevBuf<float> cols; size_t cap_cols = 0;    // the column buffers of one query
     DevBuf<char> out; size_t cap_out = 0;
 };
+struct IkBufs {
+    DevBuf<float> table;                        // the link table with joint limits, uploaded once
+    DevBuf<char> out; size_t cap_out = 0;
+};
 struct Readers {
     std::vector<double> table;                  // the RobotTable (include/pbre.h); empty: the ctx was made without a valid one
     int nl = 0, ns = 0, ndof = 0;
-    CamBufs cam; CqBufs cq; KinBufs kin;
+    CamBufs cam; CqBufs cq; KinBufs kin; IkBufs ik;
     void set_table(const double* t, size_t len) {
         if (!t || len < 24 || t[0] != 1346523717.0) return;
         const int l = (int)t[2], sp = (int)t[5];

@@ -73,6 +73,13 @@ class KinQuery(C.Structure):
                 ("jac_at_com", C.c_int32), ("qdd", C.c_void_p),
                 ("pose", C.c_void_p), ("vel", C.c_void_p), ("jac", C.c_void_p), ("mass", C.c_void_p), ("tau", C.c_void_p)]
 
+
+class IkQuery(C.Structure):
+    """pbre_ik_query_t (include/pbre_ik.h)"""
+    _fields_ = [("link", C.c_int32), ("point", C.c_float * 3), ("target_pos", C.c_void_p), ("target_quat", C.c_void_p), ("q_start", C.c_void_p),
+                ("dof_mask", C.c_void_p), ("damping", C.c_double), ("residual", C.c_double), ("rot_residual", C.c_double),
+                ("max_iters", C.c_int32), ("clamp_limits", C.c_int32), ("q", C.c_void_p), ("err", C.c_void_p), ("iters", C.c_void_p)]
+
 _LIB = None
 
 
@@ -125,6 +132,11 @@ def load(path=None):
             getattr(lib, name).restype = C.c_int
         lib.pbre_kin_query_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
         lib.pbre_kin_query.argtypes = [C.c_void_p, C.c_void_p]
+    if hasattr(lib, "pbre_ik_query"):            # the inverse-kinematics query (include/pbre_ik.h); the host emulation library has none
+        for name in ("pbre_ik_query_device", "pbre_ik_query"):
+            getattr(lib, name).restype = C.c_int
+        lib.pbre_ik_query_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+        lib.pbre_ik_query.argtypes = [C.c_void_p, C.c_void_p]
     if path is None:
         _LIB = lib
     return lib
@@ -666,6 +678,65 @@ class Engine:
             self._chk(self.lib.pbre_kin_query(self._ctx, C.byref(o)))
         return res
 
+    # ---- the inverse-kinematics query (include/pbre_ik.h; csrc/pbre_ik.hip) ----
+    def ik_query(self, target_pos, target_quat=None, link=None, point=(0, 0, 0), q_start=None, dof_mask=None, damping=None, residual=None,
+                 rot_residual=0, max_iters=None, clamp_limits=False, out="numpy", q=True, err=True, iters=True):
+        """Per env, the joint positions that bring the point `point` (link frame) of link `link` (None: the table's ee_link) to target_pos
+        [N, 3] -- and, with target_quat [N, 4] (x, y, z, w; normalised on the device), the link to that orientation; None: position only --
+        by the damped-least-squares iteration of the step (p.calculateInverseKinematics), started at q_start [N, nd] (None: the joint
+        positions of the state on the device).  Only DoFs on the chain from the root to the link move, and of those only the ones that are
+        not ik_passive and whose dof_mask byte ([nd], optional) is non-zero; the others keep their start value.  damping, residual,
+        max_iters None: the engine's ik_damping, ik_residual, ik_max_iters; rot_residual > 0 also requires the rotation error angle below
+        it; clamp_limits clamps the moved DoFs to the table's limits after every update.  Returns, each only when asked for: "q" float32
+        [N, nd], "err" float32 [N, 2] (position error in metres, rotation error angle in radians, at the returned q) and "iters" int32 [N]
+        (updates applied; max_iters: never converged).  The state is not written.  out="numpy": host arrays, synchronous.  out="torch":
+        CUDA tensors in and out on the engine's device, enqueued on torch's current stream behind whatever step was enqueued there
+        (asynchronous, no host synchronisation)."""
+        if not hasattr(self.lib, "pbre_ik_query"):
+            raise RuntimeError("ik_query: this library has no inverse-kinematics query (no pbre_ik_query symbol; the host emulation library "
+                               "has none)")
+        n, nd = self.num_envs, self.ndof
+        want = [("q", q, (n, nd), "float32"), ("err", err, (n, 2), "float32"), ("iters", iters, (n,), "int32")]
+        res, at, dev, stream = self._outputs("ik_query", want, out)
+        o = IkQuery(**at)
+        o.link = -1 if link is None else int(link)
+        for k in range(3):
+            o.point[k] = float(point[k])
+        keep = []
+
+        def array(x, shape, name):
+            if dev is not None:
+                import torch
+                a = torch.as_tensor(x, dtype=torch.float32, device=dev).contiguous()      # (a host array: uploaded on torch's current stream)
+            else:
+                a = np.ascontiguousarray(x, dtype=np.float32)
+            if tuple(a.shape) != shape:
+                raise ValueError("ik_query: %s must have shape %r, got %r" % (name, shape, tuple(a.shape)))
+            keep.append(a)
+            return a.data_ptr() if dev is not None else a.ctypes.data
+
+        o.target_pos = array(target_pos, (n, 3), "target_pos")
+        if target_quat is not None:
+            o.target_quat = array(target_quat, (n, 4), "target_quat")
+        if q_start is not None:
+            o.q_start = array(q_start, (n, nd), "q_start")
+        if dof_mask is not None:
+            mask = np.ascontiguousarray(np.asarray(dof_mask) != 0, dtype=np.uint8)
+            if mask.shape != (nd,):
+                raise ValueError("ik_query: dof_mask must have shape (%d,)" % nd)
+            keep.append(mask)
+            o.dof_mask = mask.ctypes.data
+        o.damping = -1.0 if damping is None else float(damping)
+        o.residual = -1.0 if residual is None else float(residual)
+        o.rot_residual = float(rot_residual)
+        o.max_iters = -1 if max_iters is None else int(max_iters)
+        o.clamp_limits = int(bool(clamp_limits))
+        if stream is not None:
+            self._chk(self.lib.pbre_ik_query_device(self._ctx, C.byref(o), stream))
+        else:
+            self._chk(self.lib.pbre_ik_query(self._ctx, C.byref(o)))
+        return res
+
 
 class MultiEngine(object):
     """`num_envs` environments sharded over several GPUs of one node from ONE process (the Gym classes' `devices=[...]` kwarg, SURVEY
@@ -722,6 +793,17 @@ class MultiEngine(object):
             raise NotImplementedError("kin_query(out='torch'): one device per engine (use shards[k].kin_query)")
         dd = None if qdd is None else np.ascontiguousarray(qdd, dtype=np.float32)
         parts = self._map(lambda k: self.shards[k].kin_query(qdd=None if dd is None else dd[self._sl(k)], **kw))
+        return {key: self._cat([p[key] for p in parts]) for key in parts[0]}
+
+    def ik_query(self, target_pos, target_quat=None, q_start=None, out="numpy", **kw):
+        if out != "numpy":
+            raise NotImplementedError("ik_query(out='torch'): one device per engine (use shards[k].ik_query)")
+        per_env = [None if x is None else np.ascontiguousarray(x, dtype=np.float32) for x in (target_pos, target_quat, q_start)]
+        for x in per_env:
+            if x is not None and len(x) != self.num_envs:
+                raise ValueError("ik_query: the per-env inputs must have %d rows" % self.num_envs)
+        cut = lambda x, k: None if x is None else x[self._sl(k)]
+        parts = self._map(lambda k: self.shards[k].ik_query(cut(per_env[0], k), target_quat=cut(per_env[1], k), q_start=cut(per_env[2], k), **kw))
         return {key: self._cat([p[key] for p in parts]) for key in parts[0]}
 
     def reset(self, mask=None):

@@ -96,6 +96,16 @@ class ICubTaskBase(PandaTaskBase):
             "engine observation limits differ from the Python-side limits"
         return lim
 
+    def ik_info(self, target_pos, **kw):
+        """Joint positions that bring a link of every env to a target pose, from the batched inverse-kinematics query (include/pbre_ik.h),
+        as numpy arrays: the dict of `Engine.ik_query(target_pos, **kw)` -- "q" [N, nd], "err" [N, 2], "iters" [N].  `link` also takes a
+        link name; hand_pose=True takes [N, 6] / [N, 7] hand poses in the observation's convention and applies ik_link_offset."""
+        return self._robot.ik_info(target_pos, **kw)
+
+    def ik_tensor(self, target_pos, **kw):
+        """The same without a host hop: CUDA tensors in and out on the engine's device, solved on torch's current stream."""
+        return self._robot.ik_info(target_pos, out="torch", **kw)
+
     @property
     def _tg_pose(self):
         return self._target_pose

@@ -234,6 +234,18 @@ class PandaTaskBase(Env):
         that stream they describe the state it produced) -- operational-space control, link-pose rewards, torque costs."""
         return self._robot.kinematics_info(out="torch", **kw)
 
+    def ik_info(self, target_pos, **kw):
+        """Joint positions that bring a link of every env to a target pose, from the batched inverse-kinematics query (include/pbre_ik.h),
+        as numpy arrays: the dict of `Engine.ik_query(target_pos, **kw)` -- "q" [N, nd], "err" [N, 2], "iters" [N].  `link` also takes a
+        link name; hand_pose=True takes [N, 6] / [N, 7] hand poses in the observation's convention (the joint-mode action of a Cartesian
+        plan, reachability of sampled goals)."""
+        return self._robot.ik_info(target_pos, **kw)
+
+    def ik_tensor(self, target_pos, **kw):
+        """The same without a host hop: CUDA tensors in and out on the engine's device, solved on torch's current stream (so after a
+        step_tensor on that stream the start values are the state it produced)."""
+        return self._robot.ik_info(target_pos, out="torch", **kw)
+
     # ------------------------------------------------------------------ reference attributes
     @property
     def _env_step_counter(self):

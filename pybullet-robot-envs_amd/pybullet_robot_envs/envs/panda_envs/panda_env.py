@@ -288,6 +288,16 @@ class pandaEnv:
         from pybullet_robot_envs.model.table import kin_args
         return self._engine_or_build().kin_query(**kin_args(self._model, kw))
 
+    def ik_info(self, target_pos, **kw):
+        """Joint positions that bring a link of every env to a target pose (p.calculateInverseKinematics), from the batched
+        inverse-kinematics query on the device (include/pbre_ik.h; the keyword arguments and the result of Engine.ik_query: "q", "err",
+        "iters").  `link` also takes the name of a link of the simulated model.  hand_pose=True: target_pos holds hand poses in the
+        observation's convention -- [N, 6] with Euler angles or [N, 7] with a quaternion -- of the end-effector link, i.e. what
+        apply_action commands.  Read-only, so it also answers inside a task env."""
+        from pybullet_robot_envs.model.table import ik_args
+        eng = self._engine_or_build()
+        return eng.ik_query(**ik_args(self._model, eng.cfg, dict(kw, target_pos=target_pos)))
+
     def get_object_pose(self):
         """[N, 7] position + quaternion of the object of the demo scene (the demo reads it back through PyBullet)."""
         eng = self._engine_or_build()

@@ -124,6 +124,52 @@ def kin_args(model, kw):
     return kw
 
 
+def hand_pose_target(pose, link_offset):
+    """Hand poses [N, 6] (x, y, z, roll, pitch, yaw) or [N, 7] (x, y, z, quaternion x y z w) in the observation's convention -> (target_pos
+    [N, 3], target_quat [N, 4]) of the end-effector LINK for Engine.ik_query: the orientation as given, the position moved by the constant
+    ik_link_offset of the engine's config rotated into the world (zero for the Panda; the iCub's hand pose is that of the hand's centre of
+    mass), which is what apply_action's inverse kinematics drives.  numpy arrays or torch tensors (the result stays where the input is)."""
+    xp = np
+    if not isinstance(pose, np.ndarray):
+        try:
+            import torch
+            xp = torch if isinstance(pose, torch.Tensor) else np
+        except ImportError:
+            pass
+        if xp is np:
+            pose = np.asarray(pose, dtype=np.float64)
+    if pose.ndim != 2 or pose.shape[1] not in (6, 7):
+        raise ValueError("hand_pose: [N, 6] (position, Euler angles) or [N, 7] (position, quaternion) poses, got shape %r" % (tuple(pose.shape),))
+    pos = pose[:, 0:3]
+    if pose.shape[1] == 6:                       # pybullet.getQuaternionFromEuler
+        h = pose[:, 3:6] * 0.5
+        cr, sr, cp, sp, cy, sy = xp.cos(h[:, 0]), xp.sin(h[:, 0]), xp.cos(h[:, 1]), xp.sin(h[:, 1]), xp.cos(h[:, 2]), xp.sin(h[:, 2])
+        quat = xp.stack([sr * cp * cy - cr * sp * sy, cr * sp * cy + sr * cp * sy, cr * cp * sy - sr * sp * cy, cr * cp * cy + sr * sp * sy], 1)
+    else:
+        quat = pose[:, 3:7]
+        quat = quat / xp.sqrt((quat * quat).sum(1))[:, None]
+    ox, oy, oz = (float(v) for v in link_offset)
+    x, y, z, w = quat[:, 0], quat[:, 1], quat[:, 2], quat[:, 3]
+    # R(quat) offset = o + 2 w (u x o) + 2 u x (u x o), u = (x, y, z)
+    cx, cy_, cz = y * oz - z * oy, z * ox - x * oz, x * oy - y * ox
+    dx, dy, dz = y * cz - z * cy_, z * cx - x * cz, x * cy_ - y * cx
+    off = xp.stack([ox + 2 * (w * cx + dx), oy + 2 * (w * cy_ + dy), oz + 2 * (w * cz + dz)], 1)
+    return pos + off, quat
+
+
+def ik_args(model, cfg, kw):
+    """ik_query keyword arguments from an env-level call: `link` may be a link name; with hand_pose=True, target_pos holds hand poses
+    ([N, 6] or [N, 7], hand_pose_target) of the table's end-effector link"""
+    kw = dict(kw)
+    if kw.get("link") is not None:
+        kw["link"] = link_index(model, kw["link"])
+    if kw.pop("hand_pose", False):
+        if kw.get("link") is not None or kw.get("target_quat") is not None:
+            raise ValueError("hand_pose=True: the pose is that of the end-effector link (leave link and target_quat unset)")
+        kw["target_pos"], kw["target_quat"] = hand_pose_target(kw["target_pos"], [cfg.ik_link_offset[k] for k in range(3)])
+    return kw
+
+
 def save_model_json(model, path):
     with open(path, "w") as f:
         json.dump(model, f, indent=1)
