@@ -83,7 +83,13 @@ typedef struct pbre_ctx pbre_ctx;
  * :122 (150 solver iterations), :126 (gravity); panda_env.py:76,308 (motor gains). */
 typedef struct {
     double dt, gravity_z;
-    int32_t solver_iters;
+    int32_t solver_iters;             /* sweeps of the constraint solver per simulation step; any positive count is supported, at creation and
+                                         through pbre_set_physics (tests/test_*_sweep_counts.py: 1 .. 1000).  What the Panda's simple class (envs
+                                         without robot contact) evaluates in closed form depends on it: the motor rows at even counts >= 4
+                                         (a matrix power with exponent solver_iters / 2); the tail of a resting cube's object-table rows, and
+                                         with solver_residual_threshold > 0 the scan for the exit sweep, at even counts >= PBRE_OC_K + 32
+                                         (54 as built).  At odd counts, and below these thresholds, Bullet's sequential rows run -- as they do
+                                         in every other kernel at every count; the results agree within a quarter of the single-step bounds. */
     double erp, linear_slop, contact_margin;
     double lin_damping, ang_damping, max_coord_vel;
     double max_motor_impulse, limit_max_impulse;
@@ -107,7 +113,12 @@ typedef struct {
                                          box so far], so a PyBullet-pinned comparison may need 1e-7 here.  With a value > 0 every env's
                                          constraint system is swept as ONE system (no closed form of the motor block, no split of an env
                                          over two waves, no lane-per-env iCub pipeline): the exit test is a maximum over all of its rows.
-                                         The sweeps each env ran in the last step: pbre_get_sweeps. */
+                                         The sweeps each env ran in the last step: pbre_get_sweeps.  That count is pinned (equal to the fp64
+                                         oracle's but for a bounded share of envs one or two sweeps apart) for thresholds down to 1e-9; from
+                                         about 1e-11 down it is not: the fp32 residual of the sequential rows stalls at rounding level above
+                                         such a threshold while the closed form's matrix power keeps contracting, so the two leave the loop
+                                         tens to hundreds of sweeps apart -- with joint velocities within 4e-6 rad/s of each other, the
+                                         solve having converged either way ("Sweep counts other than 150"). */
 } pbre_physics;
 
 typedef struct {

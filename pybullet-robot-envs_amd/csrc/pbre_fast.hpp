@@ -460,7 +460,17 @@ struct Fast {
     // The scan finds the first passing sweep among those it visits: every sweep from the lane's last coarse stop on, and the trial
     // pairs before it.  It would miss a sweep that passes INSIDE an earlier coarse block while the block's end does not (a residual
     // that is not decreasing in the sweep index); `mono` is cleared when the trial pairs' residuals do not decrease, and such a lane
-    // takes the explicit rows.  Out: e = the error after the exit sweep (or after sweep iters - 1); returns the sweeps used.
+    // takes the explicit rows.  Out: e = the error after the exit sweep (or, for a lane that passes nowhere, after the last pair the scan
+    // reaches); returns the sweeps used.
+    // REACH: pair 0, nine coarse steps (pairs 1 .. 73) and ten explicit pairs -- the last pair the scan can visit is 82, sweep 165.  Up to
+    // iters = 166 that is every pair (150: mlast = 74) and "passes nowhere" means e after sweep iters - 1.  Above 166 a lane that has not
+    // passed by sweep 165 returns used = iters with e after pair <= 82, although the sequential rows would go on to sweep iters - 1.  It
+    // cannot matter: e obeys a linear map without a forcing term and shrinks by a factor ~0.76 per pair (the exit sweep moves by ~16.5
+    // sweeps per factor 100 of the threshold: medians 68 / 84 / 101 at 1e-7 / 1e-9 / 1e-11, tools/rt_closed_check.py), so by pair 82 it
+    // is ~1e-10 of w0 - t, below fp32's resolution of w = t + e, and what the remaining pairs would take off it is smaller still; and a
+    // threshold low enough not to be passed by then lies far below the fp32 residual of the object's rows at sweep OC_K - 1, so the lane
+    // does not qualify in the first place (step_t: bit OC_K - 1 of opass) and takes the explicit rows.  On the emulation no lane was
+    // at the cap at 300 sweeps for thresholds down to 1e-11; tests/test_*_sweep_counts.py run 300 sweeps with the threshold on.
     static PBRE_HD int motor_scan(const float* A, const float* dinv, float* e, int iters, float tau, unsigned opass, int OK, bool& mono) {
         auto row = [&](float* v, int j, float& r) {
             r = fmaxf(r, fabsf(v[j]));

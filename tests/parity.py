@@ -138,9 +138,20 @@ def assert_within(worst, tol=None, context=""):
     assert not bad, "per-quantity tolerance exceeded (measured, bound): %r %s" % (bad, context)
 
 
+def set_solver_iters(eng, k, *oracles):
+    """The sweep count of an engine that was created and reset at the default one, and of the oracles it is compared with: without the
+    second half the oracle silently stays at 150."""
+    eng.set_physics(solver_iters=int(k))
+    assert eng.get_physics().solver_iters == k
+    for o in oracles:
+        o.params.solver_iters = int(k)
+
+
 def make_pair(Engine, lib, table, n, task=1, obj_std=0.05, tg_std=0.2, **kw):
     eng = Engine(table, task=task, num_envs=n, lib=lib, obj_pose_rnd_std=obj_std, tg_pose_rnd_std=tg_std, **kw)
     ora = orc.Oracle(table, task=task)
+    if "solver_iters" in (kw.get("phys") or {}):      # (an engine created at another sweep count: without this the oracle silently stays at 150)
+        ora.params.solver_iters = int(kw["phys"]["solver_iters"])
     ora.task.obj_pose_rnd_std = obj_std
     ora.task.tg_pose_rnd_std = tg_std
     if kw.get("use_ik"):
@@ -1007,7 +1018,7 @@ TOL_PANDA_ARM = {"q": 2e-6, "qd": 3e-4, "obj_pos": 3e-7, "obj_quat": 8e-7, "obj_
                  "obs_ee_pos": 2e-6, "obs_ee_eul": 4e-6, "obs_ee_vel": 4e-3, "obs_rest": 3e-6}
 
 
-def check_panda_arm(Engine, lib, use_ik=0, control_orientation=1, n=2, steps=4, seed=11):
+def check_panda_arm(Engine, lib, use_ik=0, control_orientation=1, n=2, steps=4, seed=11, solver_iters=None):
     """The Panda's robot-level engine (half-wave lane groups with motor records) against the oracle: reset; fused command + step
     from identical states; finger commands with a force and a velocity bound (pandaEnv.apply_action_fingers: force 10,
     maxVelocity 1, panda_env.py:218-225); apply_action(max_vel) + stepSimulation loops (helloworld_panda.py:99-140)."""
@@ -1022,6 +1033,8 @@ def check_panda_arm(Engine, lib, use_ik=0, control_orientation=1, n=2, steps=4, 
     W = 32
     mot = eng.get_motor_state()
     assert mot.shape == (n, 4, W) and np.abs(mot[:, 0, :9] - mrec[:, :9]).max() < 1e-5 and (mot[:, 3] == 0).all()
+    if solver_iters is not None:        # (everything after the reset at this sweep count, in engine and oracle)
+        set_solver_iters(eng, solver_iters, ora)
     rng = np.random.default_rng(seed)
     home = np.array([0.0, -0.54, 0.0, -2.6, -0.30, 2.0, 1.0, 0.02, 0.02])
     worst, flips = {}, 0
@@ -2341,10 +2354,12 @@ TOL_RT_FLIP = dict(TOL_CONTACT, q=5e-6, qd=1.2e-3, obj_v=4e-4, obj_w=4e-3, obs_q
 
 
 def check_residual_threshold(Engine, lib, table, states=None, n=48, steps=3, thr=1e-7, flags=0, tol=None, seed=41, max_flip=0.05, report=None,
-                             skip_ambiguous=False, max_skip=0.15, expect_early=True, **over):
+                             skip_ambiguous=False, max_skip=0.15, expect_early=True, solver_iters=None, **over):
     """One step each from identical fp32 states with the threshold on in engine and oracle.  Asserts: the engine's per-env sweep counts
     (pbre_get_sweeps) equal the oracle's except for a bounded fraction of one-sweep flips; equal-count env-steps within `tol`; flips within
-    TOL_RT_FLIP; the test actually fires (some env leaves before solver_iters) and changes the result against a full solve."""
+    TOL_RT_FLIP; the test actually fires (some env leaves before solver_iters) and changes the result against a full solve.
+    solver_iters: the sweep count the engine and the oracle are switched to AFTER the reset (which runs at the default count).
+    expect_early=None: the firing assertions hold where the ORACLE's sweep counts say that an env left early (never the engine's)."""
     rng = np.random.default_rng(seed)
     if states is None:
         eng, ora = make_pair(Engine, lib, table, n, flags=flags, **over)
@@ -2356,6 +2371,8 @@ def check_residual_threshold(Engine, lib, table, states=None, n=48, steps=3, thr
         st = np.asarray(states, np.float64)
         n = st.shape[0]
         eng, ora = make_pair(Engine, lib, table, n, flags=flags, **over)
+    if solver_iters is not None:
+        set_solver_iters(eng, solver_iters, ora)
     with_thr = lambda e: e.set_physics(solver_residual_threshold=thr)
     try:
         eng.get_sweeps()
@@ -2416,6 +2433,8 @@ def check_residual_threshold(Engine, lib, table, states=None, n=48, steps=3, thr
     if expect_early:
         assert rep["early"] > 0, "the residual test never fired: nothing tested"
         assert rep.get("max_effect_qd", 0.0) > 1e-6, "leaving the loop early changed nothing"
+    elif expect_early is None and "max_effect_qd" in rep:       # (the oracle left the loop more than 20 sweeps early in some env)
+        assert rep["max_effect_qd"] > 1e-6, "leaving the loop early changed nothing"
     assert_within(worst, tt, "(residual threshold %g: %d env-steps with equal sweep counts, %d flips, %d ambiguous skipped)" % (thr, rep["compared"], rep["flips"], rep["skipped_ambiguous"]))
     assert_within(worst_flip, TOL_RT_FLIP, "(residual threshold %g: the %d env-steps that left the loop a sweep apart)" % (thr, rep["flips"]))
     return rep
