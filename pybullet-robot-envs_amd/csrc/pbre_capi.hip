@@ -391,17 +391,8 @@ int PandaEngine::init(const pbre_config& c) {
     n = c.num_envs; npad = ceil16(n); obs_dim = obs_dim_of(T, P); act_dim = act_dim_of(c);
     ow = obs_dim + 2; device = c.device_id; sf = STATE; lc = LC;
     fast_ok = topo_matches<TopoPanda>(T) && fast_scene_ok(P);
-    if (const char* ev = getenv("PBRE_RC_FIRST_MIN")) rc_first_min = atoi(ev);       // A/B knobs
-    if (const char* ev = getenv("PBRE_IDLE_SINGLE")) idle_single = atoi(ev);
-    if (const char* ev = getenv("PBRE_KSAMPLE")) ksample = std::max(1, atoi(ev));
-    if (const char* ev = getenv("PBRE_IDLE_TOUCH")) idle_touch = atoi(ev);
-    if (const char* ev = getenv("PBRE_ROW_MAX")) row_max = atoi(ev);
-    if (const char* ev = getenv("PBRE_FAST3")) fast3 = atoi(ev);
-    if (const char* ev = getenv("PBRE_FUSED")) fused = atoi(ev);
-    if (const char* ev = getenv("PBRE_OBJV_SEQ0")) main.objv_seq = tmp.objv_seq = atoi(ev);      // (tests: start k_fused's sequence numbers next to their wrap)
-    if (const char* ev = getenv("PBRE_PAIR")) pair = atoi(ev);
-    if (const char* ev = getenv("PBRE_TAIL_PAIR")) tail_pair = atoi(ev);      // (0: A/B; n > 1: tests -- always the last n chunks)
-    if (const char* ev = getenv("PBRE_ZERO_COPY")) zero_copy = atoi(ev);
+    knobs = StepKnobs::from_env();       // A/B knobs
+    main.objv_seq = tmp.objv_seq = knobs.objv_seq0;      // (tests: start k_fused's sequence numbers next to their wrap)
     if (const int rc = open_device()) return rc;
     { hipDeviceProp_t pr; HIPCHK(hipGetDeviceProperties(&pr, device)); n_simd = std::max(1, pr.multiProcessorCount * 4); }
     HIPCHK(sp.create(0, false));
@@ -512,10 +503,10 @@ int PandaEngine::step(const float* actions, float* out) {
     // zero-copy (PBRE_ZERO_COPY bit 0: actions, bit 1: rows): a page-locked buffer (pbre_host_alloc) is accessed by the kernels
     // themselves, over PCIe, instead of being staged through HBM with a copy
     bool za = false, zo = false;
-    if (zero_copy) {
+    if (knobs.zero_copy) {
         hipPointerAttribute_t pa;
-        za = (zero_copy & 1) && hipPointerGetAttributes(&pa, actions) == hipSuccess && pa.type == hipMemoryTypeHost;
-        zo = (zero_copy & 2) && hipPointerGetAttributes(&pa, out) == hipSuccess && pa.type == hipMemoryTypeHost;
+        za = (knobs.zero_copy & 1) && hipPointerGetAttributes(&pa, actions) == hipSuccess && pa.type == hipMemoryTypeHost;
+        zo = (knobs.zero_copy & 2) && hipPointerGetAttributes(&pa, out) == hipSuccess && pa.type == hipMemoryTypeHost;
         (void)hipGetLastError();
     }
     rows_to_host = zo;

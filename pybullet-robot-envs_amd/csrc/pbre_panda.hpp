@@ -88,6 +88,7 @@ __device__ int g_wave_diag;
 #include "pbre_fast.hpp"
 #include "pbre_engine.hpp"
 #include "pbre_sidepick.hpp"
+#include "pbre_step_plan.hpp"
 
 using namespace pbre;
 using CoreD = Core<DevLanes>;
@@ -156,9 +157,9 @@ __device__ __forceinline__ void publish_class(int env, int c, signed char* __res
 // (0.249 ms per stationary step against 0.220 ms with this variant; right after reset(), without complex envs, 0.157 against 0.187).
 // launch_step picks per step.
 // (fast_wave: one wave's work -- the 64 envs of `chunk`, lane ln; k_fast's body and, round 5, the simple envs' part of k_fused)
-// CT: read the model constants through the constant address space (see Fast::step; measured first in k_fused -- 131072 envs fresh 0.101 ->
-// 0.089 ms -- then made the default of every lane-per-env step kernel; false: A/B)
-template <int MODE, bool RT, bool CT = true>
+// The model constants are read through the constant address space (CTables; see Fast::step; measured first in k_fused -- 131072 envs fresh
+// 0.101 -> 0.089 ms -- then made the way of every lane-per-env step kernel)
+template <int MODE, bool RT>
 __device__ __forceinline__ void fast_wave(const FTables* __restrict__ T, const Params& P, float* __restrict__ state,
                                           const float* __restrict__ actions, float* __restrict__ out, int n, int act_dim, int ow, int flags,
                                           const signed char* __restrict__ cls_cur, signed char* __restrict__ cls, int* __restrict__ next_list,
@@ -206,15 +207,9 @@ __device__ __forceinline__ void fast_wave(const FTables* __restrict__ T, const P
     }
 #endif
     if (env >= n || cls_cur[env] != 0) return;      // classes of the state this step starts from (the kernels of the step write the next array)
-    int c;
-    if constexpr (CT)
-        c = FastD::step<RT>(*(const CTables*)T, P, state + (size_t)env * STATE, (MODE & FastD::M_ACTION) ? actions + (size_t)env * act_dim : nullptr,
-                            (MODE & FastD::M_OBS) ? out + (size_t)env * ow : nullptr, MODE, flags, P.env_id_base + (unsigned long long)env,
-                            (MODE & FastD::M_TGT) ? tgt + (size_t)env * NJ : nullptr, (RT && P.sweeps) ? P.sweeps + env : nullptr);
-    else
-        c = FastD::step<RT>(*T, P, state + (size_t)env * STATE, (MODE & FastD::M_ACTION) ? actions + (size_t)env * act_dim : nullptr,
-                            (MODE & FastD::M_OBS) ? out + (size_t)env * ow : nullptr, MODE, flags, P.env_id_base + (unsigned long long)env,
-                            (MODE & FastD::M_TGT) ? tgt + (size_t)env * NJ : nullptr, (RT && P.sweeps) ? P.sweeps + env : nullptr);
+    const int c = FastD::step<RT>(*(const CTables*)T, P, state + (size_t)env * STATE, (MODE & FastD::M_ACTION) ? actions + (size_t)env * act_dim : nullptr,
+                                  (MODE & FastD::M_OBS) ? out + (size_t)env * ow : nullptr, MODE, flags, P.env_id_base + (unsigned long long)env,
+                                  (MODE & FastD::M_TGT) ? tgt + (size_t)env * NJ : nullptr, (RT && P.sweeps) ? P.sweeps + env : nullptr);
     publish_class(env, c, cls, next_list, next_count, cap, P.bad_count);
 }
 template <int MODE, int WPS = PBRE_FAST_WAVES, bool RT = false>
@@ -236,7 +231,7 @@ __global__ __launch_bounds__(FTPB, WPS) void k_fast(const FTables* __restrict__ 
 constexpr int PTPB = 2 * FTPB;
 // (pair_wave: one wave's work -- role 0 the robots, role 1 the objects of the 64 envs of `chunk`, exchange record px; k_fast_pair's body and,
 // round 5, the simple envs' part of k_fused<.., true>.  One block barrier per wave that has a simulating lane.)
-template <int MODE, bool CT = true>
+template <int MODE>
 __device__ __forceinline__ void pair_wave(const FTables* __restrict__ T, const Params& P, float* __restrict__ state,
                                           const float* __restrict__ actions, float* __restrict__ out, int n, int act_dim, int ow, int flags,
                                           const signed char* __restrict__ cls_cur, signed char* __restrict__ cls, int* __restrict__ next_list,
@@ -258,17 +253,11 @@ __device__ __forceinline__ void pair_wave(const FTables* __restrict__ T, const P
         float* o = (MODE & FastD::M_OBS) ? out + (size_t)env * ow : nullptr;
         const unsigned long long id = P.env_id_base + (unsigned long long)env;
         int c;
-        if constexpr (CT) {
-            if (sim) c = FastD::step_t<false, 1>(*(const CTables*)T, P, st, a, o, MODE, flags, id, (MODE & FastD::M_TGT) ? tgt + (size_t)env * NJ : nullptr, &px, ln);
-            else c = FastD::skipped(*(const CTables*)T, P, st, o, MODE, flags, id);
-        } else {
-            if (sim) c = FastD::step_t<false, 1>(*T, P, st, a, o, MODE, flags, id, (MODE & FastD::M_TGT) ? tgt + (size_t)env * NJ : nullptr, &px, ln);
-            else c = FastD::skipped(*T, P, st, o, MODE, flags, id);
-        }
+        if (sim) c = FastD::step_t<false, 1>(*(const CTables*)T, P, st, a, o, MODE, flags, id, (MODE & FastD::M_TGT) ? tgt + (size_t)env * NJ : nullptr, &px, ln);
+        else c = FastD::skipped(*(const CTables*)T, P, st, o, MODE, flags, id);
         publish_class(env, c, cls, next_list, next_count, cap, P.bad_count);
     } else {
-        if constexpr (CT) { if (sim) (void)FastD::step_t<false, 2>(*(const CTables*)T, P, st, nullptr, nullptr, MODE, flags, 0ull, nullptr, &px, ln); }
-        else if (sim) (void)FastD::step_t<false, 2>(*T, P, st, nullptr, nullptr, MODE, flags, 0ull, nullptr, &px, ln);
+        if (sim) (void)FastD::step_t<false, 2>(*(const CTables*)T, P, st, nullptr, nullptr, MODE, flags, 0ull, nullptr, &px, ln);
         if (pg) { if (sim) __hip_atomic_store((int*)((char*)pg + PBRE_PAIR_G_FLAGS) + ln, seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT); }     // its stores (state record, pg) first
         else __syncthreads();                 // its stores (state record, LDS) are complete before the robot wave goes on
     }
@@ -451,6 +440,8 @@ __global__ __launch_bounds__(RTPB, 2) void k_row_list(const Tables* __restrict__
 constexpr int FUSED_WAVES = RTPB / FTPB;
 static_assert(RTPB % FTPB == 0 && FUSED_WAVES % 2 == 0, "k_fused: whole waves, whole pairs");
 static_assert(sizeof(PairX) <= PBRE_PAIR_G_FLAGS, "a tail pair's global record: the sequence words behind the PairX");
+static_assert(PLAN_FTPB == FTPB && PLAN_REPB == REPB && PLAN_FUSED_WAVES == FUSED_WAVES && PLAN_RTPB == RTPB && PLAN_PTPB == PTPB,
+              "plan_step (pbre_step_plan.hpp) counts its grids in these kernels' blocks");
 // The arguments travel as ONE struct and each role reads them through its own (laundered) pointer into the kernarg segment.  As plain kernel
 // arguments all of them -- Params is ~600 bytes -- are loaded in the entry block and stay live in SGPRs through whichever role the block takes:
 // the first build of this kernel had 5.7 k more v_readlane_b32 (SGPRs spilled to VGPR lanes, re-read inside the sweep loops) than its two
@@ -473,8 +464,8 @@ __device__ __forceinline__ void tail_pair_role(const FusedArgs PBRE_CONST_AS* a,
     float* pg = (float*)((char*)a->pair_g + (size_t)tchunk * PBRE_PAIR_G_BYTES);
     const int seq = a->P.objv_seq;
     PBRE_LAUNDER(a);
-    pair_wave<MODE, true>(T, *(const Params*)&a->P, a->state, a->actions, a->out, a->n, a->act_dim, a->ow, a->flags, a->cls_cur, a->cls, a->next_list, a->next_count,
-                          a->cap, a->tgt, a->zero_count, *(PairX*)pg, tchunk, ln, role, pg, seq);
+    pair_wave<MODE>(T, *(const Params*)&a->P, a->state, a->actions, a->out, a->n, a->act_dim, a->ow, a->flags, a->cls_cur, a->cls, a->next_list, a->next_count,
+                    a->cap, a->tgt, a->zero_count, *(PairX*)pg, tchunk, ln, role, pg, seq);
 }
 // RT (round 6): Bullet's residual exit -- the 64-thread grid only (the pair mapping splits an env over two waves, the exit test is a maximum
 // over all of its rows); the row blocks' object waves idle (Core::step<RT> sweeps the object's rows itself).
@@ -500,7 +491,7 @@ __global__ __launch_bounds__(PAIR ? RTPB : FTPB, 2) void k_fused(const FusedArgs
         const int fb = (int)blockIdx.x - a->rblocks, wv = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)), ln = (int)(threadIdx.x & (FTPB - 1));
         PBRE_LAUNDER(a);
         __shared__ PairX px[FUSED_WAVES / 2];
-        pair_wave<MODE, true>(FT, *(const Params*)&a->P, a->state, a->actions, a->out, a->n, a->act_dim, a->ow, a->flags, a->cls_cur, a->cls, a->next_list, a->next_count, a->cap,
+        pair_wave<MODE>(FT, *(const Params*)&a->P, a->state, a->actions, a->out, a->n, a->act_dim, a->ow, a->flags, a->cls_cur, a->cls, a->next_list, a->next_count, a->cap,
                         a->tgt, a->zero_count, px[wv >> 1], fb * (FUSED_WAVES / 2) + (wv >> 1), ln, wv & 1);
     } else {
         // 64-thread blocks, like k_fast's: beside a machine-filling batch (131072 envs = 2048 waves = every wave slot) the row waves displace some
@@ -532,8 +523,8 @@ __global__ __launch_bounds__(PAIR ? RTPB : FTPB, 2) void k_fused(const FusedArgs
             }
         }
         PBRE_LAUNDER(a);
-        fast_wave<MODE, RT, true>(FT, *(const Params*)&a->P, a->state, a->actions, a->out, a->n, a->act_dim, a->ow, a->flags, a->cls_cur, a->cls, a->next_list, a->next_count,
-                               a->cap, a->tgt, a->zero_count, chunk, (int)threadIdx.x);
+        fast_wave<MODE, RT>(FT, *(const Params*)&a->P, a->state, a->actions, a->out, a->n, a->act_dim, a->ow, a->flags, a->cls_cur, a->cls, a->next_list, a->next_count,
+                            a->cap, a->tgt, a->zero_count, chunk, (int)threadIdx.x);
     }
 }
 
@@ -566,23 +557,7 @@ struct PandaEngine : pbre_ctx {
     DevBuf<float> d_scratch;
     bool fast_ok = false;
     int n_simd = 1024;
-    int rc_first_min = 1;              // complex envs (reported by the device) from which their kernel is scheduled ahead of k_fast
-    int idle_touch = 16;               // in that mode, an (empty) fork / join through the side stream every idle_touch-th step: a side stream
-                                       // left idle for hundreds of steps makes the first steps after the switch back ~8 % slower (0: never)
-    int idle_single = 1;               // with no complex envs reported, both kernels go to the caller's stream in order (no fork / join events); 0: A/B
-    int row_max = 4096;                // up to this many complex envs they are stepped by the row kernel (1 wave per 4 envs)
-    int pair = 2;                      // k_fast_pair (robot wave + object wave per 64 envs): 0 never, 1 whenever it applies, 2 while its waves fit two per SIMD (PBRE_PAIR)
-    long launches_pair = 0;
-    int tail_pair = 0;                 // k_fused's 64-thread grid: the chunks the row waves displace into a second round as robot / object wave pairs (PBRE_TAIL_PAIR: 0 never,
-                                       // 1 by the hint, n > 1: always the last n chunks -- tests).  Measured (profiles/r06s_final_structure_ab.txt, r06t_bench_tail_pairs_by_hint.json):
-                                       // by the hint the stationary mix at 131072 envs gains 1.3 % (0.1494 -> 0.1476 ms) and a batch with FEW complex envs -- synchronised
-                                       // episode clocks, ~30 per step -- loses 34 % (0.091 -> 0.122: two dozen pairs at the end of the grid start when the first round ends): off
-    long launches_tail = 0;
-    int fast3 = 2;                     // k_fast variant limited to 3 waves per SIMD: 0 never, 1 whenever complex envs are reported, 2 when they would displace k_fast waves (PBRE_FAST3)
-                                       // -- only where the step is NOT one fused launch (PBRE_FUSED=0, residual exit, action_repeat's inner steps).  (Round 5 also measured the
-                                       // spill-free build in two half-grid launches back to back, one wave per SIMD each: 0.21 ms against 0.177, profiles/r05_fast3_halves_ab.txt.)
-    int fused = 1;                     // the step as ONE launch (k_fused: row-list blocks + fast / pair blocks in one grid); 0: the two kernels on two streams (PBRE_FUSED)
-    unsigned long long launches_fused = 0;
+    StepKnobs knobs;                   // the A/B knobs (pbre_step_plan.hpp; init reads them from the environment)
     SidePick sp;
     hipStream_t side = nullptr;        // the candidate of `sp` that overlaps with the caller's stream
     // pipelined host path (pbre_step_async / pbre_step_wait, round 6): two (actions, rows) device buffer pairs and the events that order upload
@@ -598,10 +573,9 @@ struct PandaEngine : pbre_ctx {
     int async_blocks = 128;            // PBRE_ASYNC_BLOCKS: 256-thread blocks of the row-download kernel (k_rows_out)
     Event ev_fork, ev_join, ev_join_sys;   // ev_join_sys: with the system-scope fence (see pbre_step)
     bool rows_to_host = false;         // the step in flight writes its output rows straight into page-locked host memory
-    static constexpr int KSAMPLE = 8;          // every KSAMPLE-th launch is sampled into ev_k, on the stream the dominant kernel runs on
-    int ksample = KSAMPLE;                     // PBRE_KSAMPLE: A/B of the sampling interval
     long launches = 0, launches3 = 0;          // launches3: steps whose k_fast was the 3-waves-per-SIMD variant
-    int zero_copy = 3;                 // PBRE_ZERO_COPY: pbre_step lets the kernels access page-locked host buffers directly (bit 0 actions, bit 1 rows; 0: staged copies)
+    long launches_pair = 0, launches_tail = 0; // steps in the pair mapping / fused steps with tail pairs
+    unsigned long long launches_fused = 0;     // steps that were one launch (k_fused)
 
     int init(const pbre_config& c) override;
     hipError_t alloc_buf(EnvBuf& b, int cap);
@@ -646,47 +620,35 @@ hipError_t launch_step_t(PandaEngine* c, EnvBuf& b, int n, const float* act, flo
     flags |= c->cfg.flags & (PBRE_F_SEQ_MOTORS | PBRE_F_SEQ_OBJECT);
     const int cur = b.cur, nxt = cur ^ 1;
     const int cc = b.ccur, cn = (cc + 1) % 3, cz = (cc + 2) % 3;      // counters: current, next (zero on entry), the one after
-    const int blocks = (n + FTPB - 1) / FTPB;
     hipError_t e;
-    // The two kernels of a step run concurrently on two streams (fork/join events) and both append to list[nxt].
-    // Which one gets the caller's stream is a scheduling choice made from the complex-env count the device reported for
-    // an earlier step (a hint; either order is correct):
-    //  * complex envs present: k_fast_rc (few waves, each needs a whole SIMD's register file, long latency) is enqueued first on
-    //    the caller's stream so that its waves claim their SIMDs before k_fast floods the chip from the side stream;
-    //  * none (e.g. the first steps after a reset): the (empty) complex-env kernel and k_fast are enqueued in order on the caller's
-    //    stream, with no fork / join events at all: the event packets and the concurrently dispatched empty kernel cost 6 % of the
-    //    step (613 M -> 650 M env-steps/s at 131072 envs).  Taken only when the device has reported no complex env for 16 steps in a
-    //    row (a count that flickers between 0 and a few would otherwise serialise the two kernels every other step); a stale
-    //    hint only serialises them for that step.
-    const int hint = b.h_total[0];
-    // complex envs: row kernel while they are few (latency), lane-per-env k_fast_rc when many (throughput)
-    bool rows = NB <= 2 && hint <= c->row_max;
-    if (c->cfg.flags & PBRE_F_COMPLEX_ROWS) rows = NB <= 2;
-    if (c->cfg.flags & PBRE_F_COMPLEX_LANES) rows = false;
-    if (!c->P.obj_iso || c->P.obj_shape != 0) rows = NB <= 2;      // k_fast_rc's object rows assume a cube: other boxes and the round objects' complex envs go to the row kernel
-    // (the host knows the complex envs' total, not how many of them are coupled -- one env per wave: about a tenth, generously)
-    // At least 64 blocks whatever the hint says: the hint is the count of a step the DEVICE has finished, and a host that runs ahead
-    // of it (the 201 launches of a reset are enqueued in ~1 ms) sizes every launch by a count that may be a hundred steps old --
-    // 16384 envs that had all become complex meanwhile were walked by 8 blocks, 11 ms per launch.  Blocks without work exit at once.
-    const int rblocks = std::max(64, std::min(c->n_simd / 4, (hint + REPB - 1) / REPB + (NB > 1 ? std::min(hint, 8 + hint / 4) / (REPB / 4) : 0) + 8));
-    // small batches: the pair kernel (two waves per 64 envs) while all of its waves are resident at once, two per SIMD at most
-    bool pair = false;
-    if (!RT && c->pair != 0 && !(flags & PBRE_F_NO_OBJECT) && !(MODE & FastD::M_INNER))
-        pair = c->pair == 1 || 2 * blocks <= 2 * c->n_simd;
-    // (env.step() under joint control, and the settle steps of reset(): 201 launches per reset)
-    if constexpr (NB <= 2 && (MODE == MODE_STEP || MODE == 0)) {
+    // Query, plan, execute.  How the step is launched -- which kernels, which grids, which streams -- is decided by plan_step (pbre_step_plan.hpp:
+    // the rules and what each was measured against) from the complex-env count the device reported for an earlier step (a hint; every plan is
+    // correct); what follows only does what the plan says.  The `if constexpr` guards keep the kernels each (MODE, RT) instantiates what they were.
+    // (fusable: env.step() under joint control, and the settle steps of reset(): 201 launches per reset)
+    constexpr bool FUSABLE = NB <= 2 && (MODE == MODE_STEP || MODE == 0);
+    StepQuery q;
+    q.n = n; q.n_simd = c->n_simd; q.nb = NB;
+    q.hint = b.h_total[0]; q.recent = b.h_total[1];
+    q.cfg_flags = c->cfg.flags; q.step_flags = flags;
+    q.rt = RT; q.inner = (MODE & FastD::M_INNER) != 0; q.fusable = FUSABLE;
+    q.obj_iso = c->P.obj_iso != 0; q.obj_shape = c->P.obj_shape; q.action_repeat = c->cfg.action_repeat;
+    q.have_pair_g = (float*)b.pair_g != nullptr;
+    q.launches = c->launches;
+    const StepPlan p = plan_step(c->knobs, q);
+    const int ksample = c->knobs.ksample;
+    if constexpr (FUSABLE) {
         // the whole step as one launch on the caller's stream (k_fused): no fork / join through the side stream
-        if (c->fused && rows) {
-            const bool timed = (c->launches++ % c->ksample) == c->ksample - 1;
+        if (p.form != StepPlan::TWO_KERNELS) {
+            const bool timed = (c->launches++ % ksample) == ksample - 1;
             const Event* ek = c->ev_k[c->k_steps % pbre_ctx::KRING];
             if (timed) (void)hipEventRecord(ek[0], s);
             c->launches_fused++;
             FusedArgs fa = {c->dT, Pk, b.state, act, out, n, c->act_dim, c->ow, flags, b.cls + (size_t)cur * b.cap, b.cls + (size_t)nxt * b.cap, b.list[cur],
-                            b.count + cc * NB, b.list[nxt], b.count + cn * NB, b.cap, b.tgt, b.count + cz * NB, b.h_total, b.cap, b.count + 3 * NB, rblocks, b.objv_g, b.pair_g, 0};
-            if (pair) {
+                            b.count + cc * NB, b.list[nxt], b.count + cn * NB, b.cap, b.tgt, b.count + cz * NB, b.h_total, b.cap, b.count + 3 * NB, p.rblocks, b.objv_g, b.pair_g, 0};
+            if (p.form == StepPlan::FUSED_PAIR) {
                 c->launches_pair++;
-                if constexpr (!RT)      // (`pair` is never set with the residual exit)
-                hipLaunchKernelGGL((k_fused<MODE, true>), dim3(rblocks + (blocks + FUSED_WAVES / 2 - 1) / (FUSED_WAVES / 2)), dim3(RTPB), 0, s, fa, (const Tables*)c->dT, (const FTables*)c->dFT);
+                if constexpr (!RT)      // (the plan never pairs with the residual exit)
+                hipLaunchKernelGGL((k_fused<MODE, true>), dim3(p.grid_fused), dim3(p.threads_fused), 0, s, fa, (const Tables*)c->dT, (const FTables*)c->dFT);
             } else {
                 // (never 0: that value selects the block barrier, PBRE_OBJV_SYNC.  After 2^31 - 1 launches -- four days of stepping -- the numbers
                 // start over, behind a clear of the records: a record last written 2^31 launches ago must not look complete)
@@ -697,23 +659,12 @@ hipError_t launch_step_t(PandaEngine* c, EnvBuf& b, int n, const float* act, flo
                 }
                 b.objv_seq++;
                 fa.P.objv_seq = b.objv_seq;
-                // tail pairs: as many of the last chunks as the row blocks' waves (the hint's complex envs: the coupled ones -- about a quarter,
-                // generously -- one per wave, the others four, an object wave per 12) will keep k_fast waves out of the first round
-                int ntail = 0;
-                if (!RT && c->tail_pair != 0 && c->cfg.action_repeat <= 1 && !(flags & PBRE_F_NO_OBJECT) && b.pair_g) {
-                    const int coupled = NB > 1 ? std::min(hint, 8 + hint / 4) : 0;
-                    const int rw = coupled + (hint - coupled + 3) / 4 + (hint + REPB - 1) / REPB;
-                    ntail = c->tail_pair > 1 ? c->tail_pair : (hint > 0 ? blocks + rw - 2 * c->n_simd : 0);
-                    ntail = std::max(0, std::min(ntail, blocks - 1));
-                }
-                fa.ntail = ntail;
-                if (ntail) c->launches_tail++;
-                bool launched = false;
-                if constexpr (!RT) if (ntail) {
-                    hipLaunchKernelGGL((k_fused<MODE, false, false, true>), dim3(FUSED_WAVES * rblocks + blocks + ntail), dim3(FTPB), 0, s, fa, (const Tables*)c->dT, (const FTables*)c->dFT);
-                    launched = true;
-                }
-                if (!launched) hipLaunchKernelGGL((k_fused<MODE, false, RT>), dim3(FUSED_WAVES * rblocks + blocks), dim3(FTPB), 0, s, fa, (const Tables*)c->dT, (const FTables*)c->dFT);
+                fa.ntail = p.ntail;
+                if (p.ntail) c->launches_tail++;
+                if constexpr (!RT) if (p.form == StepPlan::FUSED_64_TAIL)      // (no tail pairs with the residual exit)
+                    hipLaunchKernelGGL((k_fused<MODE, false, false, true>), dim3(p.grid_fused), dim3(p.threads_fused), 0, s, fa, (const Tables*)c->dT, (const FTables*)c->dFT);
+                if (p.form == StepPlan::FUSED_64)
+                    hipLaunchKernelGGL((k_fused<MODE, false, RT>), dim3(p.grid_fused), dim3(p.threads_fused), 0, s, fa, (const Tables*)c->dT, (const FTables*)c->dFT);
             }
             if ((e = hipGetLastError()) != hipSuccess) return e;
             if (timed) { (void)hipEventRecord(ek[1], s); c->k_steps++; }
@@ -722,55 +673,47 @@ hipError_t launch_step_t(PandaEngine* c, EnvBuf& b, int n, const float* act, flo
             return hipSuccess;
         }
     }
+    // The two kernels of a step run concurrently on two streams (fork/join events) and both append to list[nxt].
     c->side = c->sp.pick(s);
-    const bool rc_first = hint >= c->rc_first_min;
-    const bool single = c->idle_single && hint == 0 && b.h_total[1] == 0;      // both kernels in order on the caller's stream
-    hipStream_t s_rc = (rc_first || single) ? s : c->side, s_fast = (rc_first && !single) ? c->side : s;
-    const bool touch_side = single && c->idle_touch > 0 && (c->launches % c->idle_touch) == 0;   // keep the side stream's queue mapped
-    if (!single || touch_side) {
+    hipStream_t s_rc = p.rc_on_caller ? s : c->side, s_fast = p.fast_on_caller ? s : c->side;
+    if (p.fork_join) {
         if ((e = hipEventRecord(c->ev_fork, s)) != hipSuccess) return e;
         if ((e = hipStreamWaitEvent(c->side, c->ev_fork, 0)) != hipSuccess) return e;
     }
     if constexpr (NB <= 2) {
-        if (rows) {
-            hipLaunchKernelGGL((k_row_list<MODE, RT>), dim3(rblocks), dim3(RTPB), 0, s_rc, c->dT, c->dFT, Pk, b.state, act, out, c->act_dim, c->ow, flags,
+        if (p.rows) {
+            hipLaunchKernelGGL((k_row_list<MODE, RT>), dim3(p.grid_rc), dim3(p.threads_rc), 0, s_rc, c->dT, c->dFT, Pk, b.state, act, out, c->act_dim, c->ow, flags,
                                b.list[cur], b.count + cc * NB, b.cls + (size_t)nxt * b.cap, b.list[nxt], b.count + cn * NB, b.cap, b.tgt, b.h_total, b.cap, b.count + 3 * NB);
         }
     }
-    if (!rows)
-        hipLaunchKernelGGL((k_fast_rc<MODE, RT>), dim3(std::min(c->n_simd, blocks + NB)), dim3(FTPB), 0, s_rc, c->dFT, Pk, b.state, act, out, c->act_dim, c->ow, flags,
+    if (!p.rows)
+        hipLaunchKernelGGL((k_fast_rc<MODE, RT>), dim3(p.grid_rc), dim3(p.threads_rc), 0, s_rc, c->dFT, Pk, b.state, act, out, c->act_dim, c->ow, flags,
                            b.list[cur], b.count + cc * NB, b.cls + (size_t)nxt * b.cap, b.list[nxt], b.count + cn * NB, b.cap, b.tgt, b.h_total, b.count + 3 * NB);
     if ((e = hipGetLastError()) != hipSuccess) return e;
-    // HIP event pair around the dominant kernel on the stream it runs on, for pbre_timing[3]; sampled (every KSAMPLE-th step):
+    // HIP event pair around the dominant kernel on the stream it runs on, for pbre_timing[3]; sampled (every ksample-th step):
     // an event record is a barrier packet the next dispatch waits for, a pair per step costs ~10% of this kernel
-    // (the last launch of every group of KSAMPLE: the first launches after a reset -- cold instruction cache, first touch of the
+    // (the last launch of every group of ksample: the first launches after a reset -- cold instruction cache, first touch of the
     // state -- are warm-up, not samples)
-    const bool timed = (c->launches++ % c->ksample) == c->ksample - 1;
+    const bool timed = (c->launches++ % ksample) == ksample - 1;
     const Event* ek = c->ev_k[c->k_steps % pbre_ctx::KRING];
     if (timed) (void)hipEventRecord(ek[0], s_fast);
-    // the 3-waves-per-SIMD variant when the complex envs' waves would push k_fast waves of the 2-wave variant into an extra round
-    bool fast3 = false;
-    if (!single && c->fast3 != 0 && !RT) {      // (RT: the sweep loop of the residual-exit variant needs ~170 live registers -- at 168 it spills inside the loop)
-        const int slots2 = 2 * c->n_simd, rw = (rows ? (hint + 3) / 4 + (hint + REPB - 1) / REPB : (hint + FTPB - 1) / FTPB * 2) + 8;
-        fast3 = c->fast3 == 1 || ((blocks + rw + slots2 - 1) / slots2 > (blocks + slots2 - 1) / slots2 && blocks + rw <= 3 * c->n_simd);
-    }
-    if (pair) {
+    if (p.pair) {
         c->launches_pair++;
         if constexpr (!(MODE & FastD::M_INNER) && !RT)      // (the inner iterations of action_repeat > 1 stay on k_fast: not instantiated; RT: one lane per env)
-        hipLaunchKernelGGL((k_fast_pair<MODE>), dim3(blocks), dim3(PTPB), 0, s_fast, c->dFT, Pk, b.state, act, out, n, c->act_dim, c->ow, flags,
+        hipLaunchKernelGGL((k_fast_pair<MODE>), dim3(p.grid_fast), dim3(p.threads_fast), 0, s_fast, c->dFT, Pk, b.state, act, out, n, c->act_dim, c->ow, flags,
                            b.cls + (size_t)cur * b.cap, b.cls + (size_t)nxt * b.cap, b.list[nxt], b.count + cn * NB, b.cap, b.tgt, b.count + cz * NB);
     } else {
-    if (fast3) c->launches3++;
-    if constexpr (!RT) if (fast3)
-        hipLaunchKernelGGL((k_fast<MODE, 3, RT>), dim3(blocks), dim3(FTPB), 0, s_fast, c->dFT, Pk, b.state, act, out, n, c->act_dim, c->ow, flags,
+    if (p.fast3) c->launches3++;
+    if constexpr (!RT) if (p.fast3)
+        hipLaunchKernelGGL((k_fast<MODE, 3, RT>), dim3(p.grid_fast), dim3(p.threads_fast), 0, s_fast, c->dFT, Pk, b.state, act, out, n, c->act_dim, c->ow, flags,
                            b.cls + (size_t)cur * b.cap, b.cls + (size_t)nxt * b.cap, b.list[nxt], b.count + cn * NB, b.cap, b.tgt, b.count + cz * NB);
-    if (!fast3)
-        hipLaunchKernelGGL((k_fast<MODE, 2, RT>), dim3(blocks), dim3(FTPB), 0, s_fast, c->dFT, Pk, b.state, act, out, n, c->act_dim, c->ow, flags,
+    if (!p.fast3)
+        hipLaunchKernelGGL((k_fast<MODE, 2, RT>), dim3(p.grid_fast), dim3(p.threads_fast), 0, s_fast, c->dFT, Pk, b.state, act, out, n, c->act_dim, c->ow, flags,
                            b.cls + (size_t)cur * b.cap, b.cls + (size_t)nxt * b.cap, b.list[nxt], b.count + cn * NB, b.cap, b.tgt, b.count + cz * NB);
     }
     if ((e = hipGetLastError()) != hipSuccess) return e;
     if (timed) { (void)hipEventRecord(ek[1], s_fast); c->k_steps++; }
-    if (!single || touch_side) {
+    if (p.fork_join) {
         // (round-2 advice) the side stream's kernel may have written rows into host memory: join through the event that keeps its
         // system-scope release, so the host sees them once the caller's stream is synchronised, whatever the buffer's coherence mode
         hipEvent_t ej = c->rows_to_host ? c->ev_join_sys : c->ev_join;
