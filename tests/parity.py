@@ -1779,6 +1779,36 @@ def check_icub_contact_states(Engine, lib, n_each=12, steps=1, seed=21, control_
     return rep
 
 
+def five_fingertip_brick(ora, info, q, tips, obj_hz):
+    """The brick's pose in the five-fingertip scene for the joints q (fingers straight, the thumb in the plane of the four tips): its
+    5 x 7.5 cm face against the five tip spheres (links `tips`, centre 16.8 mm along x, radius 7.5 mm), on the side away from the palm, the
+    shallowest tip 0.5 mm deep.  obj_hz: the brick's half height.  -> centre, quaternion, rotation matrix, (ex, ey, nrm): the face's
+    in-plane axes and the normal that points from the tips into the brick"""
+    R, p = ora.fk(q)
+    c = np.array([p[i] + R[i] @ np.array([0.0168, 0.0, 0.0]) for i in tips])
+    cen = c.mean(0)
+    _, _, vt = np.linalg.svd(c - cen)
+    ex, ey, nrm = vt[0], vt[1], vt[2]
+    assert np.abs((c - cen) @ nrm).max() < 1e-3, "the five fingertips are not coplanar"
+    palm = p[info["ee_link"]]
+    if (palm - cen) @ nrm > 0:                            # the box goes on the side away from the palm
+        nrm = -nrm
+    ex = np.cross(ey, nrm)                                # right-handed frame (box x = ey: 5 cm, box y = ex: 7.5 cm, box z = nrm)
+    u, v = (c - cen) @ ex, (c - cen) @ ey
+    mid = cen + ex * 0.5 * (u.max() + u.min()) + ey * 0.5 * (v.max() + v.min())
+    Rb = np.stack([ey, ex, -nrm] if np.linalg.det(np.stack([ey, ex, nrm], 1)) < 0 else [ey, ex, nrm], 1)
+    if np.linalg.det(Rb) < 0:
+        Rb[:, 0] = -Rb[:, 0]
+    depth = (c - cen) @ nrm                               # > 0: further into the box side
+    # face plane at cen + nrm * f: a tip sphere (radius 7.5 mm) penetrates by depth - f + 0.0075; the shallowest tip gets 0.5 mm
+    f = depth.min() + 0.0075 - 0.0005
+    centre = mid + nrm * (f + obj_hz) - nrm * ((mid - cen) @ nrm)
+    tr = Rb[0, 0] + Rb[1, 1] + Rb[2, 2]
+    qw = np.sqrt(max(1e-12, 1 + tr)) / 2
+    quat = np.array([(Rb[2, 1] - Rb[1, 2]) / (4 * qw), (Rb[0, 2] - Rb[2, 0]) / (4 * qw), (Rb[1, 0] - Rb[0, 1]) / (4 * qw), qw])
+    return centre, quat, Rb, (ex, ey, nrm)
+
+
 def check_hands_five_fingertips(Engine, lib, control_arm="r", steps=3):
     """All five fingertips of the hand on the object: fingers straight, the thumb brought into the plane of the four fingertips
     (thumb joints 1.1775 / 1.37375 / 0.785 / 0: the five tip centres are coplanar within 0.1 mm), the brick-sized box held against
@@ -1797,32 +1827,8 @@ def check_hands_five_fingertips(Engine, lib, control_arm="r", steps=3):
     pose = [0.0] * 16 + [1.1775, 1.37375, 0.785, 0.0]
     s[0, fing] = pose
     s[0, eng.v_off:eng.v_off + nd] = 0.0
-    R, p = ora.fk(s[0, :nd])
     tips = [by_joint[jn[k]] for k in (3, 7, 11, 15, 19)]
-    c = np.array([p[i] + R[i] @ np.array([0.0168, 0.0, 0.0]) for i in tips])
-    cen = c.mean(0)
-    _, _, vt = np.linalg.svd(c - cen)
-    ex, ey, nrm = vt[0], vt[1], vt[2]
-    assert np.abs((c - cen) @ nrm).max() < 1e-3, "the five fingertips are not coplanar"
-    palm = p[info["ee_link"]]
-    if (palm - cen) @ nrm > 0:                            # the box goes on the side away from the palm
-        nrm = -nrm
-    ex = np.cross(ey, nrm)                                # right-handed frame (box x = ey: 5 cm, box y = ex: 7.5 cm, box z = nrm)
-    ph = eng.get_physics()
-    u, v = (c - cen) @ ex, (c - cen) @ ey
-    mid = cen + ex * 0.5 * (u.max() + u.min()) + ey * 0.5 * (v.max() + v.min())
-    Rb = np.stack([ey, ex, -nrm] if np.linalg.det(np.stack([ey, ex, nrm], 1)) < 0 else [ey, ex, nrm], 1)
-    if np.linalg.det(Rb) < 0:
-        Rb[:, 0] = -Rb[:, 0]
-    zb = Rb[:, 2]
-    sgn = 1.0 if zb @ nrm > 0 else -1.0                  # the face that looks at the fingertips is the box's -sgn z face
-    depth = (c - cen) @ nrm                               # > 0: further into the box side
-    # face plane at cen + nrm * f: a tip sphere (radius 7.5 mm) penetrates by depth - f + 0.0075; the shallowest tip gets 0.5 mm
-    f = depth.min() + 0.0075 - 0.0005
-    centre = mid + nrm * (f + ph.obj_h[2]) - nrm * ((mid - cen) @ nrm)
-    tr = Rb[0, 0] + Rb[1, 1] + Rb[2, 2]
-    qw = np.sqrt(max(1e-12, 1 + tr)) / 2
-    quat = np.array([(Rb[2, 1] - Rb[1, 2]) / (4 * qw), (Rb[0, 2] - Rb[2, 0]) / (4 * qw), (Rb[1, 0] - Rb[0, 1]) / (4 * qw), qw])
+    centre, quat, _, _ = five_fingertip_brick(ora, info, s[0, :nd], tips, eng.get_physics().obj_h[2])
     s[0, nd:nd + 3] = centre
     s[0, nd + 3:nd + 7] = quat
     s[0, eng.v_off + nd:eng.v_off + nd + 6] = 0
