@@ -702,21 +702,24 @@ def force_bound(tail_o):
     return 2e-2 * (1.0 + np.abs(tail_o[:, :5]).max())
 
 
-def compare(names, se, ob, so, out, s_f, o_f):
+def compare(names, se, ob, so, out, s_f, o_f, shape=_Shape, tol=tol_of, groups=groups_of, tail=7):
     """per group and quantity: the engine against the fp64 oracle, bound = TOL or, where the oracle's own fp32 build misses TOL on the same
     states, max(TOL, 4 x d32); the observation tail: counts equal, forces within 4 x d32 but never looser than force_bound.
-    -> report, failures"""
+    shape, tol, groups, tail: another lane-group engine's record, tables, report groups and observation tail (tests/arm_rows.py; tail 0:
+    an engine that reports no fingertip forces).  -> report, failures"""
     rep, bad = {}, {}
-    for g, idx in groups_of(names).items():
-        tt = tol_of(g)
-        d32 = parity.group_quantities(_Shape, s_f[idx], so[idx], o_f[idx, :-2], out[idx], tail=7)
-        w = parity.group_quantities(_Shape, se[idx], so[idx], ob[idx], out[idx], tail=7)
+    for g, idx in groups(names).items():
+        tt = tol(g)
+        d32 = parity.group_quantities(shape, s_f[idx], so[idx], o_f[idx, :-2], out[idx], tail=tail)
+        w = parity.group_quantities(shape, se[idx], so[idx], ob[idx], out[idx], tail=tail)
         rep[g] = {}
         for k in tt:
-            bound = tt[k] if d32[k] <= tt[k] else max(tt[k], 4.0 * d32[k])
+            bound = float(tt[k] if d32[k] <= tt[k] else max(tt[k], 4.0 * d32[k]))
             rep[g][k] = {"engine": float("%.3g" % w[k]), "d32": float("%.3g" % d32[k]), "bound": float("%.3g" % bound)}
             if not w[k] <= bound:
                 bad.setdefault(g, {})[k] = (float("%.3g" % w[k]), bound)
+        if not tail:
+            continue
         te, to, tf = ob[idx, -7:], out[idx, -9:-2], o_f[idx, -9:-2]
         if not np.array_equal(te[:, 5:], to[:, 5:]):
             bad.setdefault(g, {})["tips in contact, contact points"] = (te[:, 5:].tolist(), to[:, 5:].tolist())

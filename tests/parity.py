@@ -1100,14 +1100,30 @@ def check_panda_arm(Engine, lib, use_ik=0, control_orientation=1, n=2, steps=4, 
 TOL_ICUB_ARM = dict(TOL_ICUB)      # measured on the lane emulation: q 8e-8, qd 1.2e-5, EE velocity 1e-5 m/s, everything else <= 3e-7
 
 
-def make_icub_arm_pair(Engine, lib, n, control_arm="l", use_ik=0, control_orientation=1, **kw):
+def make_icub_arm_pair(Engine, lib, n, control_arm="l", use_ik=0, control_orientation=1, reset=True, **kw):
     """iCubEnv used alone (pbre_config.robot_level = 1; reference icub_env.py:91-151, 259-360): engine (built by the drop-in class)
-    + oracle, same scene."""
+    + oracle, same scene.  reset=False: the engine as its constructor leaves it, for checks that set state and motor record themselves
+    (tests/arm_rows.py).  The drop-in class builds its engine and resets it in one go (202 settle steps per env); the engine is still
+    built by that code, with its arguments, and only the new INSTANCE answers that one reset() without doing anything."""
     from pybullet_robot_envs import _client
-    from pybullet_robot_envs.envs.icub_envs.icub_env import iCubEnv
+    from pybullet_robot_envs.envs.icub_envs import icub_env
     cid = _client.connect(n, lib=lib)
-    robot = iCubEnv(cid, use_IK=use_ik, control_arm=control_arm, control_orientation=control_orientation)
-    eng = robot._robot_level()
+    robot = icub_env.iCubEnv(cid, use_IK=use_ik, control_arm=control_arm, control_orientation=control_orientation)
+    if reset:
+        eng = robot._robot_level()
+    else:
+        make = icub_env._capi.make_engine
+
+        def make_unreset(*a, **k):
+            e = make(*a, **k)
+            e.reset = lambda mask=None: None
+            return e
+        icub_env._capi.make_engine = make_unreset
+        try:
+            eng = robot._robot_level()
+        finally:
+            icub_env._capi.make_engine = make
+        del eng.reset                      # the class's reset() again
     ora, tbl, info = orc.icub_arm_oracle(control_arm, use_ik, control_orientation)
     ph = eng.get_physics()
     for f in ("table_c", "table_h", "obj_h", "obj_inertia"):
@@ -1223,6 +1239,10 @@ def run_panda_demo(robot, upto=4):
     return poses
 
 
+# the Panda's robot-level engine with robot-object contacts, one step from identical states (check_panda_arm_grasp, tests/arm_rows.py)
+TOL_PANDA_ARM_CONTACT = {"q": 2e-5, "qd": 5e-3, "obj_pos": 5e-6, "obj_quat": 5e-5}
+
+
 def check_panda_arm_grasp(Engine, lib, n=1, steps=3):
     """Robot-object contacts of the Panda's robot-level engine against the oracle: the demo is run up to the closed grasp (both
     fingers squeezing the object: force-limited, velocity-limited finger motors, 2-4 robot-object contacts + object-table contacts),
@@ -1259,7 +1279,7 @@ def check_panda_arm_grasp(Engine, lib, n=1, steps=3):
         tail_e, tail_o = ob[:, -7:], out[:, -9:-2]
         assert np.array_equal(tail_e[:, 5:], tail_o[:, 5:]), (tail_e, tail_o)                     # fingers in contact, contact points
         assert np.abs(tail_e[:, :5] - tail_o[:, :5]).max() < 2e-2 * (1.0 + np.abs(tail_o[:, :5]).max()), (tail_e, tail_o)
-        assert q["q"] < 2e-5 and q["qd"] < 5e-3 and q["obj_pos"] < 5e-6 and q["obj_quat"] < 5e-5, q
+        assert all(q[k] < v for k, v in TOL_PANDA_ARM_CONTACT.items()), q
         seen = max(seen, int(tail_o[:, 6].max()))
         st, mrec = so, mrec2
     assert seen >= 2
