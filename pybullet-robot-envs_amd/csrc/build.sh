@@ -8,7 +8,7 @@ HIPCC=${HIPCC:-/opt/rocm/bin/hipcc}
 FLAGS="--offload-arch=gfx950 -O3 -std=c++17 -fPIC -fno-fast-math -fno-slp-vectorize -Rpass-analysis=kernel-resource-usage $PBRE_EXTRA_FLAGS"
 JOBS=${PBRE_BUILD_JOBS:-$(nproc)}
 mkdir -p obj
-HDRS="pbre_math.hpp pbre_sidepick.hpp pbre_core.hpp pbre_objstep.hpp pbre_fast.hpp pbre_lane.hpp pbre_host.hpp pbre_tables.hpp pbre_devmem.hpp pbre_devwork.hpp pbre_engine.hpp pbre_wide_impl.hpp lanes_device.hpp pbre_comm_impl.hpp pbre_panda.hpp pbre_step_plan.hpp pbre_camera.hpp pbre_scene.hpp pbre_contacts.hpp pbre_kin.hpp pbre_ik.hpp ../../include/pbre.h ../../include/pbre_camera.h ../../include/pbre_contacts.h ../../include/pbre_kin.h ../../include/pbre_ik.h build.sh"
+HDRS="pbre_math.hpp pbre_sidepick.hpp pbre_core.hpp pbre_objstep.hpp pbre_fast.hpp pbre_lane.hpp pbre_host.hpp pbre_tables.hpp pbre_devmem.hpp pbre_devwork.hpp pbre_engine.hpp pbre_wide_impl.hpp lanes_device.hpp pbre_comm_impl.hpp pbre_panda.hpp pbre_step_plan.hpp pbre_reset_seq.hpp pbre_camera.hpp pbre_scene.hpp pbre_contacts.hpp pbre_kin.hpp pbre_ik.hpp ../../include/pbre.h ../../include/pbre_camera.h ../../include/pbre_contacts.h ../../include/pbre_kin.h ../../include/pbre_ik.h build.sh"
 # name:source:extra flags   (the residual-exit instantiations first: they are the longest)
 UNITS=""
 for rt in true false; do for m in 2 0 3 1 4 5; do UNITS="$UNITS pbre_step_${m}_${rt}:pbre_step_inst.hip:-DPBRE_INST_MODE=${m}@-DPBRE_INST_RT=${rt}"; done; done

@@ -74,20 +74,21 @@ __global__ void k_snapshot_reset(const Tables* __restrict__ T, const Params P, f
     if (e < n && mask[e]) CoreD::snapshot_reset(*T, P, P.env_id_base + (unsigned long long)e, state + (size_t)e * STATE);
 }
 // episode number of the next reset of env idx[i]: one more than the episode stored in its record (-1 = never reset)
-// (also hands the env's per-env object parameters X[12], X[13], X[15] -- which a reset keeps -- to the record it is re-initialised in)
-__global__ void k_next_episode(const float* __restrict__ state, const int* __restrict__ idx, int cnt, int cpad, unsigned* __restrict__ ep,
-                               float* __restrict__ work) {
+// (also hands the floats a reset keeps -- the Panda's per-env object parameters X[12], X[13], X[15], V[15] -- to the record the env is
+// re-initialised in; records cnt .. cpad - 1 repeat the last env).  sf floats per record, the episode at X[5]
+__global__ void k_next_episode(const float* __restrict__ state, const int* __restrict__ idx, int cnt, int cpad, int sf, unsigned* __restrict__ ep,
+                               float* __restrict__ work, const ResetKeep keep) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= cpad) return;
-    const float* src = state + (size_t)idx[i < cnt ? i : cnt - 1] * STATE;
-    ep[i] = (unsigned)((int)src[37] + 1);
-    if (work != state) { float* dst = work + (size_t)i * STATE; dst[44] = src[44]; dst[45] = src[45]; dst[47] = src[47]; dst[31] = src[31]; }
+    const float* src = state + (size_t)idx[i < cnt ? i : cnt - 1] * sf;
+    ep[i] = (unsigned)((int)src[sf - 16 + 5] + 1);
+    if (work != state) for (int k = 0; k < keep.n; k++) work[(size_t)i * sf + keep.slot[k]] = src[keep.slot[k]];
 }
-// dst[idx[i]] <- src[i], 48 floats per record
-__global__ void k_scatter(float* __restrict__ dst, const float* __restrict__ src, const int* __restrict__ idx, int cnt) {
+// dst[idx[i]] <- src[i], sf floats per record
+__global__ void k_scatter(float* __restrict__ dst, const float* __restrict__ src, const int* __restrict__ idx, int cnt, int sf) {
     const int t = blockIdx.x * blockDim.x + threadIdx.x;
-    const int i = t / STATE, k = t % STATE;
-    if (i < cnt) dst[(size_t)idx[i] * STATE + k] = src[(size_t)i * STATE + k];
+    const int i = t / sf, k = t % sf;
+    if (i < cnt) dst[(size_t)idx[i] * sf + k] = src[(size_t)i * sf + k];
 }
 
 static thread_local std::string g_err;      // errors without a ctx (pbre_create): per calling thread (MultiEngine creates its shards from one thread per device)
@@ -210,6 +211,52 @@ int pbre_ctx::observe(float* obs) {
     HIPCHK(hipGetLastError());
     HIPCHK(hipMemcpy2DAsync(obs, (size_t)obs_dim * 4, d_out, (size_t)ow * 4, (size_t)obs_dim * 4, n, hipMemcpyDeviceToHost, stream));
     HIPCHK(hipStreamSynchronize(stream));
+    return PBRE_OK;
+}
+hipError_t pbre_ctx::scatter_records(float* dst, const float* src, int cnt, int floats) {
+    hipLaunchKernelGGL(k_scatter, dim3((cnt * floats + 255) / 256), dim3(256), 0, stream, dst, src, d_idx, cnt, floats);
+    return hipGetLastError();
+}
+// The selected envs (null: all) begin their next episode: reset_sequence (pbre_reset_seq.hpp) on the batch in place or, for a part of it,
+// on a compacted copy in the scratch buffer that is scattered back
+int pbre_ctx::reset(const uint8_t* mask) {
+    HIPCHK(hipSetDevice(device));
+    HIPCHK(quiesce());
+    std::vector<int> idx;
+    for (int e = 0; e < n; e++) if (!mask || mask[e]) idx.push_back(e);
+    const int cnt = (int)idx.size(), cpad = (cnt + rst_keep.pad - 1) / rst_keep.pad * rst_keep.pad;
+    if (cnt == 0) return PBRE_OK;
+    std::vector<unsigned long long> ids(cpad);
+    for (int i = 0; i < cpad; i++) ids[i] = P.env_id_base + (unsigned long long)idx[i < cnt ? i : cnt - 1];
+    HIPCHK(hipMemcpyAsync(d_ids, ids.data(), (size_t)cpad * 8, hipMemcpyHostToDevice, stream));
+    HIPCHK(hipMemcpyAsync(d_idx, idx.data(), (size_t)cnt * 4, hipMemcpyHostToDevice, stream));
+    // episode numbers live in the state records (the device advances them on auto-reset)
+    const bool full = cnt == n;
+    hipLaunchKernelGGL(k_next_episode, dim3((cpad + 127) / 128), dim3(128), 0, stream, state, d_idx, cnt, cpad, sf, d_ep, full ? state : scratch, rst_keep);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(stream));          // host vectors go out of scope below
+    if (const int rc = reset_sequence(P.robot, P.use_ik != 0, P.task, mrec, cfg.flags, [&](ResetOp op, int count, int flags) {
+            const hipError_t e = reset_op(op, !full, cnt, count, flags);
+            return e == hipSuccess ? PBRE_OK : hip_fail("pbre_reset", e);
+        })) return rc;
+    if (!full) { HIPCHK(scatter_records(state, scratch, cnt, sf)); HIPCHK(reset_scattered(cnt)); }
+    HIPCHK(hipStreamSynchronize(stream));
+    if (!full) return PBRE_OK;
+    // snapshot for PBRE_F_AUTO_RESET: settled robot pose and object height (identical in every env)
+    std::vector<float> rec(sf);
+    HIPCHK(hipMemcpy(rec.data(), state, (size_t)sf * sizeof(float), hipMemcpyDeviceToHost));
+    HIPCHK(record_snapshot(rec.data()));
+    have_snapshot = true; stale_snapshot = false;
+    P.rst_ok = 0;
+    if (restarts_in_kernel()) {   // the settled end-effector pose (the first 6 observation entries of env 0); valid while no env of the batch is complex
+        launch_observe_all(stream);
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipStreamSynchronize(stream));
+        int nc = 1;
+        HIPCHK(hipMemcpy(P.rst_ee, d_out, sizeof P.rst_ee, hipMemcpyDeviceToHost));
+        HIPCHK(complex_now(&nc));
+        P.rst_ok = nc == 0 ? 1 : 0;
+    }
     return PBRE_OK;
 }
 int pbre_ctx::reset_snapshot(const uint8_t* mask) {
@@ -410,7 +457,8 @@ int PandaEngine::init(const pbre_config& c) {
     HIPCHK(upload_tables());
     HIPCHK(alloc_buf(main, npad));
     HIPCHK(alloc_buf(tmp, npad));
-    state = main.state;
+    state = main.state; scratch = tmp.state;
+    rst_keep = {EPB, 4, {44, 45, 47, 31}};      // groups of 16 records; the per-env object parameters X[12], X[13], X[15] and V[15] (pbre_set_physics_per_env)
     if (const int rc = alloc_step_io((size_t)npad)) return rc;
     HIPCHK(hipMalloc(d_scratch.out(), 64 * sizeof(float)));
     if (const int rc = alloc_counters((size_t)npad)) return rc;
@@ -436,66 +484,35 @@ int PandaEngine::settle(int32_t count, int32_t flags) {
     return PBRE_OK;
 }
 
+// reset(): reset_sequence's operations on the first cnt envs of `main` or `tmp` (k_init / k_target: whole groups of 16 records)
+hipError_t PandaEngine::reset_op(ResetOp op, bool in_scratch, int cnt, int count, int flags) {
+    EnvBuf& b = in_scratch ? tmp : main;
+    const int cpad = ceil16(cnt);
+    if (op == RS_INIT) hipLaunchKernelGGL(k_init, dim3((cpad + 127) / 128), dim3(128), 0, stream, dT, P, b.state, d_ids, d_ep, cpad);
+    if (op == RS_HOME_IK) hipLaunchKernelGGL(k_ik<true>, dim3((cnt + FTPB - 1) / FTPB), dim3(FTPB), 0, stream, dFT, P, b.state, (const float*)nullptr, b.tgt, cnt, act_dim);
+    if (op == RS_TARGETS) hipLaunchKernelGGL(k_target, dim3((cpad + 127) / 128), dim3(128), 0, stream, P, b.state, d_ids, d_ep, cpad);
+    hipError_t e = hipGetLastError();
+    // classes depend on whether the object is present: built for the fresh records (the robot alone) and again when a run of steps changes it
+    const int cf = op == RS_INIT ? PBRE_F_NO_OBJECT : flags;
+    if (e == hipSuccess && (op == RS_INIT || (op == RS_SETTLE && cf != rst_cls_flags))) { rst_cls_flags = cf; e = classify(b, cnt, cf, stream); }
+    return (e == hipSuccess && op == RS_SETTLE) ? settle_steps(b, cnt, count, flags, stream) : e;
+}
+hipError_t PandaEngine::record_snapshot(const float* rec) {
+    for (int k = 0; k < NJ; k++) { P.rst_q[k] = rec[k]; T.rst_q[k] = rec[k]; }
+    P.rst_objz = rec[11];
+    return upload_tables();
+}
+hipError_t PandaEngine::complex_now(int* count) {
+    int cn[NB] = {0};
+    const hipError_t e = lane_per_env(this) ? hipMemcpy(cn, main.count + main.ccur * NB, sizeof cn, hipMemcpyDeviceToHost) : hipSuccess;
+    *count = 0;
+    for (int k = 0; k < NB; k++) *count += cn[k];
+    return e;
+}
 int PandaEngine::reset(const uint8_t* mask) {
-    HIPCHK(hipSetDevice(device));
-    HIPCHK(quiesce());
-    std::vector<int> idx;
-    for (int e = 0; e < n; e++) if (!mask || mask[e]) idx.push_back(e);
-    const int cnt = (int)idx.size();
-    if (cnt > 0) {
-        const int cpad = ceil16(cnt);
-        std::vector<unsigned long long> ids(cpad);
-        for (int i = 0; i < cpad; i++) ids[i] = P.env_id_base + (unsigned long long)idx[i < cnt ? i : cnt - 1];
-        HIPCHK(hipMemcpyAsync(d_ids, ids.data(), (size_t)cpad * 8, hipMemcpyHostToDevice, stream));
-        HIPCHK(hipMemcpyAsync(d_idx, idx.data(), (size_t)cnt * 4, hipMemcpyHostToDevice, stream));
-        // episode numbers live in the state records (the device advances them on auto-reset)
-        const bool full = cnt == n;
-        EnvBuf& work = full ? main : tmp;           // a partial reset settles a compacted copy
-        hipLaunchKernelGGL(k_next_episode, dim3((cpad + 127) / 128), dim3(128), 0, stream, main.state, d_idx, cnt, cpad, d_ep, work.state);
-        HIPCHK(hipGetLastError());
-        HIPCHK(hipStreamSynchronize(stream));          // host vectors go out of scope below
-        const int f0 = cfg.flags & PBRE_F_NO_OBJECT;
-        hipLaunchKernelGGL(k_init, dim3((cpad + 127) / 128), dim3(128), 0, stream, dT, P, work.state, d_ids, d_ep, cpad);
-        HIPCHK(hipGetLastError());
-        // reset_simulation (panda_push_gym_env.py:117-148): 100 steps robot alone, then world loaded: 100 + 1 steps
-        HIPCHK(classify(work, cnt, PBRE_F_NO_OBJECT, stream));
-        if (P.use_ik) {     // pandaEnv.reset with use_IK (panda_env.py:83-91): IK targets of the home hand pose + one step
-            hipLaunchKernelGGL(k_ik<true>, dim3((cnt + FTPB - 1) / FTPB), dim3(FTPB), 0, stream, dFT, P, work.state, (const float*)nullptr, work.tgt, cnt, act_dim);
-            HIPCHK(hipGetLastError());
-            HIPCHK(settle_steps(work, cnt, 1, PBRE_F_NO_OBJECT, stream));
-        }
-        HIPCHK(settle_steps(work, cnt, 100, PBRE_F_NO_OBJECT, stream));
-        if (!f0) HIPCHK(classify(work, cnt, 0, stream));
-        HIPCHK(settle_steps(work, cnt, 101, f0, stream));
-        hipLaunchKernelGGL(k_target, dim3((cpad + 127) / 128), dim3(128), 0, stream, P, work.state, d_ids, d_ep, cpad);
-        HIPCHK(hipGetLastError());
-        if (!full) {
-            hipLaunchKernelGGL(k_scatter, dim3((cnt * STATE + 255) / 256), dim3(256), 0, stream, main.state, work.state, d_idx, cnt);
-            HIPCHK(hipGetLastError());
-            HIPCHK(classify(main, n, f0, stream));
-        }
-        HIPCHK(hipStreamSynchronize(stream));
-        if (full) {   // snapshot for PBRE_F_AUTO_RESET: settled robot pose and object height (identical in every env)
-            float rec[STATE];
-            HIPCHK(hipMemcpy(rec, main.state, sizeof rec, hipMemcpyDeviceToHost));
-            for (int k = 0; k < NJ; k++) { P.rst_q[k] = rec[k]; T.rst_q[k] = rec[k]; }
-            P.rst_objz = rec[11];
-            HIPCHK(upload_tables());
-            have_snapshot = true; stale_snapshot = false;
-            // end-effector pose of the settled robot (the first 6 observation entries of env 0) for the in-kernel restart
-            launch_observe_all(stream);
-            HIPCHK(hipGetLastError());
-            HIPCHK(hipStreamSynchronize(stream));
-            float row[6]; int complex_now[NB] = {0};
-            HIPCHK(hipMemcpy(row, d_out, sizeof row, hipMemcpyDeviceToHost));
-            if (lane_per_env(this)) HIPCHK(hipMemcpy(complex_now, main.count + main.ccur * NB, sizeof complex_now, hipMemcpyDeviceToHost));
-            for (int k = 0; k < 6; k++) P.rst_ee[k] = row[k];
-            int nc = 0; for (int k = 0; k < NB; k++) nc += complex_now[k];
-            P.rst_ok = nc == 0 ? 1 : 0;         // every env of the freshly reset batch is in the simple class
-        }
-    }
+    const int rc = pbre_ctx::reset(mask);
     k_steps = 0; launches = 0; launches3 = 0; launches_pair = 0; launches_fused = 0; launches_tail = 0;      // pbre_timing[3] averages env steps only, not the settle launches above
-    return PBRE_OK;
+    return rc;
 }
 
 int PandaEngine::step(const float* actions, float* out) {
@@ -632,11 +649,9 @@ int PandaEngine::kernel_info(int32_t* info, int32_t cnt) const {
     int complex_now = 0, complex_sum = 0;       // envs whose current state is "complex" (what the next step's k_fast_rc will take)
     const bool lpe = lane_per_env(this);
     if (lpe) {
-        int cn[NB] = {0};
         (void)hipSetDevice(device); (void)hipDeviceSynchronize();
-        (void)hipMemcpy(cn, main.count + main.ccur * NB, NB * sizeof(int), hipMemcpyDeviceToHost);
+        (void)const_cast<PandaEngine*>(this)->complex_now(&complex_now);
         (void)hipMemcpy(&complex_sum, main.count + 3 * NB + 1, sizeof(int), hipMemcpyDeviceToHost);
-        for (int k = 0; k < NB; k++) complex_now += cn[k];
     }
     const int bad = read_bad();
     const int v[16] = {lpe ? rf : -1, rg, lpe ? 1 : 0, lpe ? n - complex_now : 0, lpe ? 0 : n, complex_now, lpe ? rr : -1, complex_sum,

@@ -9,6 +9,7 @@
 #include <string>
 #include "pbre_devmem.hpp"
 #include "pbre_host.hpp"
+#include "pbre_reset_seq.hpp"
 #include "pbre_scene.hpp"
 
 // the one HIP error check of the library, with an engine `eng`; HIPCHK is its spelling inside a method of an engine.  (Set-up helpers that
@@ -26,6 +27,7 @@ struct StateView {
     const float* hull;
     void* stream;         // a hipStream_t
 };
+struct ResetKeep { int pad, n, slot[4]; };      // pbre_ctx::rst_keep (by value to the next-episode kernel)
 }  // namespace pbre
 
 struct pbre_ctx {
@@ -34,6 +36,9 @@ struct pbre_ctx {
     int n = 0, obs_dim = 0, act_dim = 0, ow = 0, device = 0;
     int sf = 0, lc = 0;                       // floats per state record, float of the object's pose in it
     float* state = nullptr;                   // [n][sf] the batch's records (a view: the engine's buffers own them)
+    float* scratch = nullptr;                 // ... and as many in which a partial reset settles a compacted copy of the selected envs
+    bool mrec = false;                        // the shape keeps persistent motor records (the robot-level interfaces)
+    pbre::ResetKeep rst_keep = {1, 0, {0}};   // reset: a multiple of `pad` records is initialised (the last env repeated); n floats of its record an env keeps
     pbre::DevBuf<float> d_act, d_out;         // staging of pbre_step's actions / rows
     pbre::DevBuf<int> d_bad;                  // NaN / Inf guard: env-steps that met a non-finite state (Params::bad_count)
     pbre::DevBuf<float> d_hull;               // PBRE_SHAPE_HULL: the object's vertex / face table (Params::hull; pbre_set_object_hull)
@@ -96,7 +101,7 @@ struct pbre_ctx {
     virtual int kernel_info(int32_t* info, int32_t cnt) const = 0;
 
     // ---- entry points whose substance differs between the engines
-    virtual int reset(const uint8_t* mask) = 0;
+    virtual int reset(const uint8_t* mask);   // (written once, pbre_capi.hip; an engine's override brackets it)
     virtual int settle(int32_t count, int32_t flags) = 0;
     virtual int reset_snapshot(const uint8_t* mask);
     virtual int step(const float* actions, float* out) { const int rc = begin_step(); return rc ? rc : timed_step(actions, out, false, false); }
@@ -113,6 +118,16 @@ struct pbre_ctx {
     virtual int motor_state(float* out, const float*) {
         return fail(PBRE_E_UNSUPPORTED, out ? "pbre_get_motor_state: only the robot-level engines keep a motor record" : "pbre_set_motor_state: only the robot-level engines keep a motor record");
     }
+
+    // ---- hooks of reset(): one operation of reset_sequence on the first cnt records of the batch in place or of the scratch buffer; what
+    // is left to do once a partial reset's records are scattered back; the settled record of env 0 into rst_q / rst_objz of the uploaded
+    // tables; whether steps restart envs in-kernel (rst_ee / rst_ok) and, if so, how many envs of the batch are complex now
+    hipError_t scatter_records(float* dst, const float* src, int cnt, int floats);      // dst[d_idx[i]] <- src[i], i < cnt
+    virtual hipError_t reset_op(pbre::ResetOp op, bool in_scratch, int cnt, int count, int flags) = 0;
+    virtual hipError_t reset_scattered(int cnt) = 0;
+    virtual hipError_t record_snapshot(const float* rec) = 0;
+    virtual bool restarts_in_kernel() const = 0;
+    virtual hipError_t complex_now(int* count) = 0;
 };
 
 namespace pbre {

@@ -8,6 +8,7 @@
 #include <cstring>
 #include <string>
 #include "../../include/pbre.h"
+#include "pbre_math.hpp"
 #include "pbre_tables.hpp"
 
 namespace pbre {
@@ -172,6 +173,34 @@ inline float apply_action_cmd(Params& P, double max_vel) {
     P.cmd_vmax = vm;
     if (P.robot == PBRE_ROBOT_PANDA && vm > 0.f) { P.cmd_kp = 0.1f; P.cmd_nj = 7; }
     return vm;
+}
+// pbre_set_motors as the engines take it (the device: by value to its kernel).  Returns null or why the call is refused.
+struct MotorCmd { int n; int dof[64]; float target[64]; float kp, fscale, vmax; };
+inline const char* make_motor_cmd(MotorCmd& cmd, int cnt, const int32_t* dofs, const float* targets, double kp, double max_force, double max_vel,
+                                  int ndof, const pbre_physics& phys) {
+    if (cnt > 64) return "pbre_set_motors: more than 64 joints";
+    cmd.n = cnt; cmd.kp = (float)kp; cmd.vmax = max_vel > 0 ? (float)max_vel : 0.f;
+    cmd.fscale = max_force > 0 ? (float)(max_force * phys.dt / phys.max_motor_impulse) : 1.f;
+    for (int k = 0; k < cnt; k++) {
+        if (dofs[k] < 0 || dofs[k] >= ndof) return "pbre_set_motors: bad DoF index";
+        cmd.dof[k] = dofs[k]; cmd.target[k] = targets[k];
+    }
+    return nullptr;
+}
+// The writers of a motor record m = target[W] | kp[W] | force scale[W] | max velocity[W], one lane / commanded joint per call (a thread on the
+// device, a loop in the lane emulation): a freshly reset env (icub_env_with_hands.py:108-121: initial positions, gain 0.2, default force), the
+// joint-control half of apply_action (icub_env.py:341-361: clipped absolute targets, gain 0.5, default force), pbre_set_motors
+template <class S>
+PBRE_HD void mrec_init(const TablesT<S>& T, float* m, int l) { m[l] = T.home[l]; m[S::W + l] = T.kp_hold[l]; m[2 * S::W + l] = 1.f; m[3 * S::W + l] = 0.f; }
+template <class S>
+PBRE_HD void mrec_cmd_joint(const TablesT<S>& T, float* m, int l, const float* act, float vmax) {
+    const int k = T.act_idx[l];
+    if (k < 0) return;
+    m[l] = fminf(fmaxf(act[k], T.lower[l]), T.upper[l]); m[S::W + l] = T.kp_act[l]; m[2 * S::W + l] = 1.f; m[3 * S::W + l] = vmax;
+}
+template <class S>
+PBRE_HD void mrec_set(float* m, const MotorCmd& cmd, int k) {
+    m[cmd.dof[k]] = cmd.target[k]; m[S::W + cmd.dof[k]] = cmd.kp; m[2 * S::W + cmd.dof[k]] = cmd.fscale; m[3 * S::W + cmd.dof[k]] = cmd.vmax;
 }
 // what pbre_create returns for an error text of make_tables
 inline int table_error_code(const std::string& e) {

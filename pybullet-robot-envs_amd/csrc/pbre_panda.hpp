@@ -590,6 +590,12 @@ struct PandaEngine : pbre_ctx {
     const char* physics_objection(const Params& P2) const override { return fast_ok && !fast_scene_ok(P2) ? "the lane-per-env kernels need explicit joint damping" : nullptr; }
     void limits(float* lo, float* hi) const override { obs_limits(cfg, T, lo, hi); }
     int kernel_info(int32_t* info, int32_t cnt) const override;
+    int rst_cls_flags = 0;             // reset(): the object's presence the buffer being settled is classified for
+    hipError_t reset_op(ResetOp op, bool in_scratch, int cnt, int count, int flags) override;
+    hipError_t reset_scattered(int) override { return state_changed(); }
+    hipError_t record_snapshot(const float* rec) override;
+    bool restarts_in_kernel() const override { return true; }
+    hipError_t complex_now(int* count) override;
     int reset(const uint8_t* mask) override;
     int settle(int32_t count, int32_t flags) override;
     int step(const float* actions, float* out) override;

@@ -20,16 +20,6 @@
 
 namespace pbre {
 
-__global__ void kw_next_episode(const float* __restrict__ state, const int* __restrict__ idx, int cnt, unsigned* __restrict__ ep, int sf) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < cnt) ep[i] = (unsigned)((int)state[(size_t)idx[i] * sf + (sf - 16) + 5] + 1);
-}
-__global__ void kw_scatter(float* __restrict__ dst, const float* __restrict__ src, const int* __restrict__ idx, int cnt, int sf) {
-    const int t = blockIdx.x * blockDim.x + threadIdx.x;
-    const int i = t / sf, k = t % sf;
-    if (i < cnt) dst[(size_t)idx[i] * sf + k] = src[(size_t)i * sf + k];
-}
-
 hipError_t WideEngine::wstep(int kind, float* st, float* tg, int cnt, const float* act, float* out, int flags, hipStream_t s, bool timed) {
     const Event* ek = ev_k[k_steps % KRING];
     if (timed) (void)hipEventRecord(ek[0], s);
@@ -83,6 +73,7 @@ int WideEngine::init(const pbre_config& c) {
     HIPCHK(hipMalloc(state_buf.out(), ne * sf * sizeof(float)));
     state = state_buf;
     HIPCHK(hipMalloc(tmp.out(), ne * sf * sizeof(float)));
+    scratch = tmp;
     HIPCHK(hipMalloc(tgt.out(), ne * tg * sizeof(float)));
     HIPCHK(hipMalloc(tgt_tmp.out(), ne * tg * sizeof(float)));
     HIPCHK(hipMemset(tgt, 0, ne * tg * sizeof(float)));
@@ -116,72 +107,19 @@ int WideEngine::settle(int32_t count, int32_t flags) {
     HIPCHK(hipStreamSynchronize(stream));
     return PBRE_OK;
 }
-int WideEngine::reset(const uint8_t* mask) {
-    HIPCHK(hipSetDevice(device));
-    HIPCHK(quiesce());
-    lane_invalidate();
-    std::vector<int> idx;
-    for (int e = 0; e < n; e++) if (!mask || mask[e]) idx.push_back(e);
-    const int cnt = (int)idx.size();
-    if (cnt > 0) {
-        std::vector<unsigned long long> ids(cnt);
-        for (int i = 0; i < cnt; i++) ids[i] = P.env_id_base + (unsigned long long)idx[i];
-        hipStream_t s = stream;
-        HIPCHK(hipMemcpyAsync(d_ids, ids.data(), (size_t)cnt * 8, hipMemcpyHostToDevice, s));
-        HIPCHK(hipMemcpyAsync(d_idx, idx.data(), (size_t)cnt * 4, hipMemcpyHostToDevice, s));
-        hipLaunchKernelGGL(kw_next_episode, dim3((cnt + 127) / 128), dim3(128), 0, s, state, d_idx, cnt, d_ep, sf);
-        HIPCHK(hipGetLastError());
-        HIPCHK(hipStreamSynchronize(s));                      // host vectors go out of scope below
-        const bool full = cnt == n;
-        float* st = full ? state : (float*)tmp;               // a partial reset settles a compacted copy
-        float* tg = full ? tgt : tgt_tmp;
-        const int f0 = cfg.flags & PBRE_F_NO_OBJECT;
-        launch_init(st, cnt, s);
-        launch_mrec_init(tg, cnt, s);
-        HIPCHK(hipGetLastError());
-        // iCubEnv.reset (icub_env.py:88-151): joints at their initial positions, IK targets of the home hand pose when
-        // use_IK, one stepSimulation; then reset_simulation (icub_reach_gym_env.py:135-148): 100 steps robot alone,
-        // world loaded, 100 + 1 steps
-        if (P.use_ik) {
-            launch_ik(true, st, nullptr, tg, cnt, s);
-            HIPCHK(hipGetLastError());
-        }
-        HIPCHK(wsettle(st, tg, cnt, (P.use_ik || P.robot != PBRE_ROBOT_PANDA ? 1 : 0) + 100, PBRE_F_NO_OBJECT, s));
-        HIPCHK(wsettle(st, tg, cnt, 101, f0, s));
-        launch_target(st, cnt, s);
-        HIPCHK(hipGetLastError());
-        if (P.task >= 1) {   // iCubPushGymEnv.reset (icub_push_gym_env.py:124-127): distances the normalised reward divides by
-            launch_observe(true, st, nullptr, cnt, s);
-            HIPCHK(hipGetLastError());
-        }
-        if (!full) {
-            // the IK targets of the reset envs are only needed while settling; the next step recomputes them
-            hipLaunchKernelGGL(kw_scatter, dim3((cnt * sf + 255) / 256), dim3(256), 0, s, state, st, d_idx, cnt, sf);
-            if (mrec) hipLaunchKernelGGL(kw_scatter, dim3((cnt * tgs + 255) / 256), dim3(256), 0, s, tgt, tg, d_idx, cnt, tgs);   // motors persist
-            HIPCHK(hipGetLastError());
-        }
-        HIPCHK(hipStreamSynchronize(s));
-        if (full) {   // snapshot for PBRE_F_AUTO_RESET: settled robot pose and object height (identical in every env)
-            std::vector<float> rec(sf);
-            HIPCHK(hipMemcpy(rec.data(), state, (size_t)sf * sizeof(float), hipMemcpyDeviceToHost));
-            snapshot(rec.data());
-            HIPCHK(upload_tables());
-            have_snapshot = true; stale_snapshot = false;
-            // end-effector pose of the settled robot (the first 6 observation entries of env 0) for the lane-per-env pipeline's in-kernel
-            // restart (Lane::finish): valid while the settled state is in the simple class (no robot sphere at the object)
-            P.rst_ok = 0;
-            if (lane_ok() && !mrec) {
-                launch_observe_all(s);
-                HIPCHK(hipGetLastError());
-                HIPCHK(hipStreamSynchronize(s));
-                float row[6]; int vg = 0, cn = 1;
-                HIPCHK(hipMemcpy(row, d_out, sizeof row, hipMemcpyDeviceToHost));
-                for (int k = 0; k < 6; k++) P.rst_ee[k] = row[k];
-                if (lane_info(&vg, &cn) && cn == 0) P.rst_ok = 1;
-            }
-        }
+// reset(): reset_sequence's operations on the batch (state, tgt) or the scratch buffers (tmp, tgt_tmp)
+hipError_t WideEngine::reset_op(ResetOp op, bool in_scratch, int cnt, int count, int flags) {
+    float* st = in_scratch ? (float*)tmp : state;
+    float* tg = in_scratch ? (float*)tgt_tmp : (float*)tgt;
+    switch (op) {
+        case RS_INIT: launch_init(st, cnt, stream); break;
+        case RS_MOTORS: launch_mrec_init(tg, cnt, stream); break;
+        case RS_HOME_IK: launch_ik(true, st, nullptr, tg, cnt, stream); break;
+        case RS_SETTLE: return wsettle(st, tg, cnt, count, flags, stream);
+        case RS_TARGETS: launch_target(st, cnt, stream); break;
+        case RS_INITD: launch_observe(true, st, nullptr, cnt, stream); break;
     }
-    return PBRE_OK;
+    return hipGetLastError();
 }
 int WideEngine::reset_snapshot(const uint8_t* mask) {
     if (mrec) return fail(PBRE_E_UNSUPPORTED, "pbre_reset_snapshot: task envs only (the robot-level interfaces have no episodes)");
@@ -189,15 +127,8 @@ int WideEngine::reset_snapshot(const uint8_t* mask) {
 }
 int WideEngine::set_motors(int32_t cnt, const int32_t* dofs, const float* targets, double kp, double max_force, double max_vel, const uint8_t* mask) {
     if (!mrec) return fail(PBRE_E_UNSUPPORTED, "pbre_set_motors: only the robot-level engines keep a motor record");
-    if (cnt > 64) return fail(PBRE_E_ARG, "pbre_set_motors: more than 64 joints");
     MotorCmd cmd;
-    cmd.n = cnt; cmd.kp = (float)kp;
-    cmd.fscale = max_force > 0 ? (float)(max_force * cfg.phys.dt / cfg.phys.max_motor_impulse) : 1.f;
-    cmd.vmax = max_vel > 0 ? (float)max_vel : 0.f;
-    for (int k = 0; k < cnt; k++) {
-        if (dofs[k] < 0 || dofs[k] >= ndof()) return fail(PBRE_E_ARG, "pbre_set_motors: bad DoF index");
-        cmd.dof[k] = dofs[k]; cmd.target[k] = targets[k];
-    }
+    if (const char* no = make_motor_cmd(cmd, cnt, dofs, targets, kp, max_force, max_vel, ndof(), cfg.phys)) return fail(PBRE_E_ARG, no);
     if (cnt == 0) return PBRE_OK;
     HIPCHK(hipSetDevice(device));
     HIPCHK(quiesce());

@@ -21,7 +21,6 @@ constexpr int WTPB = 256;                        // 4 independent waves per bloc
 static_assert(WTPB == 64 * DevLanes128::WPB, "DevLanes128 sizes its per-wave LDS regions for this block size");
 template <class S> constexpr int phys_lanes() { return S::W > 64 ? 64 : S::W; }
 static_assert(Shape32::LC >= 16, "DevLanes32::sum_obj assumes the object lanes lie in the upper 16-lane row of the half-wave");   // physical lanes of one env group (Shape128: two virtual lanes each)
-struct MotorCmd { int n; int dof[64]; float target[64]; float kp, fscale, vmax; };     // pbre_set_motors, by value
 
 // RT: pbre_physics.solver_residual_threshold > 0 (Core::step<RT>; objv is null then: the exit test is over all rows of an env)
 template <class S, class L, int MODE, bool RT = false>
@@ -86,33 +85,27 @@ __global__ void kw_init(const TablesT<S>* __restrict__ T, const Params P, float*
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i < cnt) Core<L, S>::init_state(*T, P, ids[i], ep[i], state + (size_t)i * S::STATE);
 }
-// motor record of a freshly reset env (iCubHandsEnv.reset, icub_env_with_hands.py:108-121): initial positions, gain 0.2, default force
+// the motor records' writers (pbre_host.hpp), a thread per (env, lane) / (env, commanded joint)
 template <class S>
 __global__ void kw_mrec_init(const TablesT<S>* __restrict__ T, float* __restrict__ tgt, int cnt) {
     const int t = blockIdx.x * blockDim.x + threadIdx.x;
     const int i = t / S::W, l = t % S::W;
     if (i >= cnt) return;
-    float* m = tgt + (size_t)i * S::TGT;
-    m[l] = T->home[l]; m[S::W + l] = T->kp_hold[l]; m[2 * S::W + l] = 1.f; m[3 * S::W + l] = 0.f;
+    mrec_init<S>(*T, tgt + (size_t)i * S::TGT, l);
 }
-// joint-control half of apply_action without the simulation step (icub_env.py:341-361): clipped absolute targets, gain 0.5, default force
 template <class S>
 __global__ void kw_cmd_joints(const TablesT<S>* __restrict__ T, float* __restrict__ tgt, const float* __restrict__ actions, int n, int act_dim, float vmax) {
     const int t = blockIdx.x * blockDim.x + threadIdx.x;
     const int e = t / 64, l = t % 64;
     if (e >= n || l >= S::W) return;              // (64 threads per env cover the <= 64 DoF lanes; the Panda's shape has 32 lanes)
-    const int k = T->act_idx[l];
-    if (k < 0) return;
-    float* m = tgt + (size_t)e * S::TGT;
-    m[l] = fminf(fmaxf(actions[(size_t)e * act_dim + k], T->lower[l]), T->upper[l]); m[S::W + l] = T->kp_act[l]; m[2 * S::W + l] = 1.f; m[3 * S::W + l] = vmax;
+    mrec_cmd_joint<S>(*T, tgt + (size_t)e * S::TGT, l, actions + (size_t)e * act_dim, vmax);
 }
 template <class S>
 __global__ void kw_set_motors(float* __restrict__ tgt, int n, const MotorCmd cmd, const unsigned char* __restrict__ mask) {
     const int t = blockIdx.x * blockDim.x + threadIdx.x;
     const int e = t / 64, k = t % 64;
     if (e >= n || k >= cmd.n || (mask && !mask[e])) return;
-    float* m = tgt + (size_t)e * S::TGT;
-    m[cmd.dof[k]] = cmd.target[k]; m[S::W + cmd.dof[k]] = cmd.kp; m[2 * S::W + cmd.dof[k]] = cmd.fscale; m[3 * S::W + cmd.dof[k]] = cmd.vmax;
+    mrec_set<S>(tgt + (size_t)e * S::TGT, cmd, k);
 }
 // pbre_reset_snapshot (see pbre_capi.hip k_snapshot_reset); iCub push: the initial distances X[12], X[13] of the re-initialised envs are
 // taken from `initd`, a copy of the batch on which the M_INITD observation was run
@@ -136,7 +129,6 @@ __global__ void kw_target(const Params P, float* __restrict__ state, const unsig
 // the launches that depend on the shape (WideImpl below)
 struct WideEngine : pbre_ctx {
     int nj = 0, tgs = 0;                      // tgs: floats per env of the motor-target buffer
-    bool mrec = false;                        // the shape keeps persistent motor records (iCub with hands)
     DevBuf<float> state_buf, tmp, tgt, tgt_tmp;
     DevBuf<float> objv;                       // [n][W] side records of kw_obj, or null: object rows always solved in kw_step
     const float* obj_done = nullptr;          // state buffer whose object solve rode along with the last kw_ik launch (consumed by the next step)
@@ -154,7 +146,6 @@ struct WideEngine : pbre_ctx {
     virtual void launch_set_motors(const MotorCmd& cmd, const unsigned char* mask, hipStream_t s) = 0;
     virtual void launch_cmd_joints(const float* act, float vmax, hipStream_t s) = 0;
     virtual int ndof() const = 0;
-    virtual void snapshot(const float* rec) = 0;
     virtual int vgprs() const = 0;
     // lane-per-env path (pbre_lane.hpp; the Shape32 engine of pbre_wide.hip overrides these): steps of the whole batch on `state`
     virtual bool lane_ok() const { return false; }
@@ -172,7 +163,12 @@ struct WideEngine : pbre_ctx {
     void launch_observe_all(hipStream_t s) override { launch_observe(false, state, d_out, n, s); }
     void launch_snapshot_reset(const unsigned char* mask, hipStream_t s) override { snapshot_reset_kernels(mask, s); }
     int kernel_info(int32_t* info, int32_t cnt) const override;
-    int reset(const uint8_t* mask) override;
+    int reset(const uint8_t* mask) override { lane_invalidate(); return pbre_ctx::reset(mask); }
+    hipError_t reset_op(ResetOp op, bool in_scratch, int cnt, int count, int flags) override;
+    // (the IK targets of the reset envs are only needed while settling, the next step recomputes them; motor records persist)
+    hipError_t reset_scattered(int cnt) override { return mrec ? scatter_records(tgt, tgt_tmp, cnt, tgs) : hipSuccess; }
+    bool restarts_in_kernel() const override { return lane_ok() && !mrec; }      // the lane-per-env pipeline (Lane::finish)
+    hipError_t complex_now(int* count) override { int vg = 0; if (!lane_info(&vg, count)) *count = 1; return hipSuccess; }
     int settle(int32_t count, int32_t flags) override;
     int reset_snapshot(const uint8_t* mask) override;
     int set_motors(int32_t cnt, const int32_t* dofs, const float* targets, double kp, double max_force, double max_vel, const uint8_t* mask) override;
@@ -260,9 +256,10 @@ struct WideImpl : WideEngine {
         if (S::MREC) hipLaunchKernelGGL((kw_cmd_joints<S>), dim3((n * 64 + 255) / 256), dim3(256), 0, s, dT, tgt, act, n, act_dim, vmax);
     }
     int ndof() const override { return T.ndof; }
-    void snapshot(const float* rec) override {
+    hipError_t record_snapshot(const float* rec) override {
         for (int k = 0; k < S::NJ; k++) { T.rst_q[k] = rec[k]; P.rst_q[k] = rec[k]; }
         P.rst_objz = rec[S::LC + 2];
+        return upload_tables();
     }
     void limits(float* lo, float* hi) const override { obs_limits(cfg, T, lo, hi); }
     int vgprs() const override {

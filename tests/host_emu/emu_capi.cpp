@@ -27,6 +27,7 @@ extern "C" void pbre_ik_probe_hist(long* h, int clear) {
 }
 #endif
 #include "../../pybullet-robot-envs_amd/csrc/pbre_host.hpp"
+#include "../../pybullet-robot-envs_amd/csrc/pbre_reset_seq.hpp"
 #include "../../pybullet-robot-envs_amd/csrc/pbre_core.hpp"
 static long g_oc_stats[2] = {0, 0};      // lanes that failed / passed the validity bound of the object block's closed form (Fast::obj_closed)
 #define PBRE_OC_PROBE(ok) (g_oc_stats[(ok) ? 1 : 0]++)
@@ -195,28 +196,31 @@ struct Emu : pbre_ctx {
     }
     void settle_all(int cnt, int flags) override { for (int e = 0; e < n; e++) settle(e, cnt, flags); }
     void reset(const uint8_t* mask) override {
+        int cnt = 0;
         for (int e = 0; e < n; e++) {
             float* st = &state[(size_t)e * STATE];
+            float* m = &tgt[(size_t)e * TG];
             if (mask && !mask[e]) continue;
+            cnt++;
             unsigned long long id = P.env_id_base + (unsigned long long)e;
             unsigned ep = (unsigned)((int)st[2 * W + 5] + 1);      // episode numbers live in the state records
-            CoreH::init_state(T, P, id, ep, st);
-            if (S::MREC) {     // iCubHandsEnv.reset (icub_env_with_hands.py:108-121): every motor at its initial position, gain 0.2, default force
-                float* m = &tgt[(size_t)e * TG];
-                for (int l = 0; l < W; l++) { m[l] = T.home[l]; m[W + l] = T.kp_hold[l]; m[2 * W + l] = 1.f; m[3 * W + l] = 0.f; }
-            }
-            if (P.use_ik) ik(st, nullptr, &tgt[(size_t)e * TG], true);
-            // one extra stepSimulation at the end of robot.reset: Panda in IK mode (panda_env.py:91), iCub always (icub_env.py:151)
-            if (P.use_ik || P.robot != PBRE_ROBOT_PANDA) settle(e, 1, PBRE_F_NO_OBJECT);
-            settle(e, 100, PBRE_F_NO_OBJECT);                       // robot alone (panda_push_gym_env.py:129-133)
-            settle(e, 101, cfg.flags & PBRE_F_NO_OBJECT);           // world loaded: 100 + 1 steps (:136-148)
-            CoreH::sample_target(P, id, ep, st);
-            if (P.robot != PBRE_ROBOT_PANDA && P.task >= 1) {
-                auto Q = L::load(st), V = L::load(st + W), X = L::loadm(st + 2 * W, L::lti(L::lane(), 16));
-                CoreH::observe(T, P, st, Q, V, X, nullptr, CoreH::M_INITD);
-            }
+            // the sequence the device engines run (csrc/pbre_reset_seq.hpp), env by env
+            reset_sequence(P.robot, P.use_ik != 0, P.task, S::MREC, cfg.flags, [&](ResetOp op, int count, int flags) {
+                switch (op) {
+                    case RS_INIT: CoreH::init_state(T, P, id, ep, st); break;
+                    case RS_MOTORS: for (int l = 0; l < W; l++) mrec_init<S>(T, m, l); break;
+                    case RS_HOME_IK: ik(st, nullptr, m, true); break;
+                    case RS_SETTLE: settle(e, count, flags); break;
+                    case RS_TARGETS: CoreH::sample_target(P, id, ep, st); break;
+                    case RS_INITD: {
+                        auto Q = L::load(st), V = L::load(st + W), X = L::loadm(st + 2 * W, L::lti(L::lane(), 16));
+                        CoreH::observe(T, P, st, Q, V, X, nullptr, CoreH::M_INITD);
+                    }
+                }
+                return 0;
+            });
         }
-        if (!mask) {
+        if (cnt == n) {      // (as on the device: also a mask of all ones)
             for (int k = 0; k < NJ; k++) { P.rst_q[k] = state[k]; T.rst_q[k] = state[k]; } P.rst_objz = state[S::LC + 2]; have_snapshot = true; stale_snapshot = false;
             std::vector<float> row(obs_dim + 2);
             float* st = &state[0];
@@ -281,23 +285,18 @@ struct Emu : pbre_ctx {
             float* m = &tgt[(size_t)e * TG];
             const float* a = actions + (size_t)e * act_dim;
             if (P.use_ik) ik(&state[(size_t)e * STATE], a, m, false);
-            else for (int l = 0; l < T.ndof; l++) {
-                const int k = T.act_idx[l];
-                if (k < 0) continue;
-                m[l] = std::fmin(std::fmax(a[k], T.lower[l]), T.upper[l]); m[W + l] = T.kp_act[l]; m[2 * W + l] = 1.f; m[3 * W + l] = panda ? 0.f : vm;
-            }
+            else for (int l = 0; l < T.ndof; l++) mrec_cmd_joint<S>(T, m, l, a, panda ? 0.f : vm);
         }
         P = P0;
         return PBRE_OK;
     }
     int set_motors(int cnt, const int32_t* dofs, const float* targets, double kp, double max_force, double max_vel, const uint8_t* mask) override {
         if (!S::MREC) { err = "pbre_set_motors: only the robot-level engines keep a motor record"; return PBRE_E_UNSUPPORTED; }
-        for (int k = 0; k < cnt; k++) if (dofs[k] < 0 || dofs[k] >= T.ndof) { err = "pbre_set_motors: bad DoF index"; return PBRE_E_ARG; }
-        const float fs = max_force > 0 ? (float)(max_force * cfg.phys.dt / cfg.phys.max_motor_impulse) : 1.f;
+        MotorCmd cmd;
+        if (const char* no = make_motor_cmd(cmd, cnt, dofs, targets, kp, max_force, max_vel, T.ndof, cfg.phys)) { err = no; return PBRE_E_ARG; }
         for (int e = 0; e < n; e++) {
             if (mask && !mask[e]) continue;
-            float* m = &tgt[(size_t)e * TG];
-            for (int k = 0; k < cnt; k++) { m[dofs[k]] = targets[k]; m[W + dofs[k]] = (float)kp; m[2 * W + dofs[k]] = fs; m[3 * W + dofs[k]] = max_vel > 0 ? (float)max_vel : 0.f; }
+            for (int k = 0; k < cnt; k++) mrec_set<S>(&tgt[(size_t)e * TG], cmd, k);
         }
         return PBRE_OK;
     }
